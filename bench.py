@@ -17,7 +17,10 @@ same hypotheses on their shards with one RCCL allreduce of the int32[4096] count
 float sums run over the ranks' inlier segments in global order.
 
 value = useful point-plane tests (PCL iterations x global active points, summed over rounds) / s,
-whole job.  Roofline: the pruned scoring launch against HBM with SURVEY 8(d)'s algorithmic bytes,
+whole job.  A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given and prints the result line (its roofline figures come from the timed
+steps' own event times).  Everything below takes runs of its own and is measured only with --full.
+Roofline: the pruned scoring launch against HBM with SURVEY 8(d)'s algorithmic bytes,
 with its PMC traffic, issue view and the work the pruning leaves (pruned_work).  Extra lines in
 the same JSON object: refit_fast (DLG_REFIT_FAST, an exact least-squares refit -- NOT PCL's
 arithmetic: its planes differ from PCL's), incl_index_build (the Morton copy + spheres rebuilt
@@ -59,6 +62,16 @@ def parse():
     ap.add_argument("--min-inliers", type=int, default=500)
     ap.add_argument("--refit", choices=["pcl", "fast"], default="pcl",
                     help="pcl (default): PCL's float refit, bit-exact; fast: exact LS refit (not PCL)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the "
+                         "other refit mode, the index-build-inclusive steps, the pruning's work, "
+                         "the PCL walk's own timing, the PMC summaries under profiles/, the C5 "
+                         "secondary and the CPU baseline (each can be left out with its --no-* "
+                         "option).  Without it the run sets up, warms up, times --steps steps and "
+                         "prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (coeffs, offsets, inliers) as "
+                         "DIR/<name>.npy after the timed steps")
     ap.add_argument("--cpu-hyps", type=int, default=1024,
                     help="hypotheses in the single-thread CPU-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=16,
@@ -83,7 +96,10 @@ def parse():
                     help="skip the C5 (normals + NORMAL_PLANE + post-process) secondary measurement")
     ap.add_argument("--dry-ranks", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the result line's figures are per timed step)")
+    return a
 
 
 def c5_secondary(D, ctx, a):
@@ -190,6 +206,27 @@ def c5_secondary(D, ctx, a):
     out["post_absorbed"] = int(sum(x.size for x in po[1]))
     out["post_remaining"] = int(po[2].size)
     return out
+
+
+DUMP_MAX_INLIERS = 12_000_000  # 48 MB of float32 (96 MB of float64: sampled down to 48 MB)
+
+
+def dump_outputs(d: str, e: dict, global_points: int) -> None:
+    """--dump-outputs: what extract_planes returned to the caller in the last timed step, as
+    DIR/coeffs.npy (float32 [P, 4]), DIR/offsets.npy ([P + 1]) and DIR/inliers.npy (the ids of all
+    planes' inliers, plane after plane).  Ids and offsets are stored as float32 where every value
+    is exact in it (below 2^24), as float64 otherwise.  An inlier list too long for the budget is
+    cut to a fixed seeded sample of its positions (ascending, the same for equal lengths)."""
+    os.makedirs(d, exist_ok=True)
+    ft = np.float32 if global_points <= (1 << 24) else np.float64
+    inl = e["inliers"]
+    cap = DUMP_MAX_INLIERS if ft is np.float32 else DUMP_MAX_INLIERS // 2
+    if inl.size > cap:
+        pos = np.sort(np.random.default_rng(20240607).choice(inl.size, cap, replace=False))
+        inl = inl[pos]
+    np.save(os.path.join(d, "coeffs.npy"), np.asarray(e["coeffs"], np.float32))
+    np.save(os.path.join(d, "offsets.npy"), e["offsets"].astype(ft))
+    np.save(os.path.join(d, "inliers.npy"), inl.astype(ft))
 
 
 def launch_ranks(n: int, argv: list[str]) -> int:
@@ -329,8 +366,14 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = ctx.allreduce_max(elapsed)
     score_ms_max = ctx.allreduce_max(score_ms)
+    if a.dump_outputs and rank == 0:
+        # before anything below runs further steps into inl_buf
+        dump_outputs(a.dump_outputs, e, global_points)
     walk_note = "timed with events on its dispatch in the timed steps"
-    if not a.no_events and a.events == 2 and a.refit == "pcl":
+    # (event level 2 leaves the PCL walk untimed in the timed steps: its time is then known, and
+    # taken out of the memory-bound phase below, only in a --full run)
+    walk_known = a.full or a.no_events or a.events == 1 or a.refit != "pcl"
+    if a.full and not a.no_events and a.events == 2 and a.refit == "pcl":
         # the walk's own events cost the stream ~0.1 ms/step (C3): it is timed in a few extra
         # steps after the timed region instead, scaled to the timed steps' count
         ctx.set_profiling(1)
@@ -349,7 +392,7 @@ def main():
     rounds_per_step = int(e["stats"]["rounds"])
 
     extras = {}
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         def timed_steps(fn, k):
             ctx.barrier()
             ctx.synchronize()
@@ -528,6 +571,10 @@ def main():
                     "note": "the bytes the implementation's passes move (counted per pass, "
                             "bench.py), not PMC"},
         "ms_per_step": round(mb_ms / a.steps, 3)}
+    if not walk_known:
+        roofline["memory_bound_passes"]["note"] = (
+            "this phase's time includes the PCL refit's walk (latency-bound, not a memory-bound "
+            "pass), which only a --full run times and takes out")
     if walk_ms > 0:
         roofline["memory_bound_passes"]["excluded"] = {
             "refit_walk_ms_per_step": round(walk_ms / a.steps, 3),
@@ -537,7 +584,7 @@ def main():
     # over separate rocprofv3 --pmc passes of `bench.py --steps 1`), when present
     for fname, key in (("score_traffic.json", "traffic"), ("score_issue.json", "issue_view")):
         f = os.path.join(ROOT, "profiles", fname)
-        if os.path.exists(f) and a.points == 10_000_000 and not strong:
+        if a.full and os.path.exists(f) and a.points == 10_000_000 and not strong:
             try:
                 tj = json.load(open(f))
                 if key == "traffic":
@@ -559,11 +606,11 @@ def main():
                 pass
 
     secondary = None
-    if world == 1 and not a.no_secondary:
+    if a.full and world == 1 and not a.no_secondary:
         secondary = c5_secondary(D, ctx, a)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         from oracle import oracle as O
         model = platform.processor() or platform.machine()
         try:

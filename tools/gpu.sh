@@ -9,8 +9,9 @@
 #   gputests                              the whole -m gpu suite
 #   smoke                                 __graft_entry__.smoke()
 #   ab[=n,D,rounds]                       tools/score_ab.py (pruned exact vs bf16 tile scorers)
-#   bench[=extra args, comma-separated]   bench.py --steps 10 --warmup 3 (+ args)
-#   benchfull                             bench.py as the driver runs it (defaults)
+#   bench[=extra args, comma-separated]   bench.py --full --steps 10 --warmup 3 (+ args)
+#   benchfull                             bench.py --full with its default steps (every figure)
+#   benchplain                            bench.py as the driver runs it (the headline alone)
 #   prof[=extra bench args]               rocprofv3 --kernel-trace --stats over a short bench
 #   pmclds                                LDS counters (instructions, bank conflicts, LDS-busy and
 #                                         LDS-issue-stall cycles) of the scoring launch, one pass
@@ -55,8 +56,9 @@ for s in "$@"; do
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
     ab) run ab_$(echo "$arg" | tr -c 'a-zA-Z0-9_\n' '_' | cut -c1-30) 300 env PRUNE_STATS=1 python3 -u tools/score_ab.py ${arg//,/ } ;;
     bench) run bench_$(echo "$arg" | tr -c 'a-zA-Z0-9_\n' '_' | cut -c1-40)_$(echo "$arg" | md5sum | cut -c1-6) 900 \
-             python3 -u bench.py --steps 10 --warmup 3 ${arg//,/ } ;;
-    benchfull) run benchfull 900 python3 -u bench.py ;;
+             python3 -u bench.py --full --steps 10 --warmup 3 ${arg//,/ } ;;
+    benchfull) run benchfull 900 python3 -u bench.py --full ;;
+    benchplain) run benchplain 300 python3 -u bench.py ;;
     prof) run prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- \
             python3 bench.py --steps 5 --warmup 2 --no-secondary --no-extras --no-cpu-baseline ${arg//,/ } ;;
     pmc)
