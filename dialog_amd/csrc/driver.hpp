@@ -1,4 +1,4 @@
-// driver.hpp -- host-side state shared by the RANSAC driver (driver.cpp) and the normals driver
+// driver.hpp -- host-side state shared by the RANSAC driver (driver.cpp, segment.cpp) and the normals driver
 // (normals_host.cpp): error type, device/pinned buffers, the context and cloud objects.
 #pragma once
 
@@ -159,17 +159,18 @@ using namespace dlg;
 
 // execution-path options of a context (dlg_ctx_set_option).  Every combination gives the same
 // results: they only select among equivalent paths (tests run each against the oracle).
+// (All ints, booleans as 0 / 1: one member type for the option table in driver.cpp.)
 struct PathOptions {
   int prune = -1;       // Morton copy + pruned scoring: -1 clouds >= 131072 points, 0 never, 1 always
-  bool lean = true;     // lean-list rounds (single-pass selects driven by the Morton copy)
-  bool spec_pick = true;  // device pick for probability-1 rounds
-  bool prune_np = true;   // pruned NORMAL_PLANE scoring
+  int lean = 1;      // lean-list rounds (single-pass selects driven by the Morton copy)
+  int spec_pick = 1;   // device pick for probability-1 rounds
+  int prune_np = 1;    // pruned NORMAL_PLANE scoring
   int score_kernel = kScoreBf16;  // exhaustive scorer: kScoreBf16 or kScoreExact
-  bool prune_stats = false;       // accumulate the pruned kernel's work counters (dlg_prune_stats)
+  int prune_stats = 0;         // accumulate the pruned kernel's work counters (dlg_prune_stats)
   int sel1_tile = 16384;          // points per single-pass select tile (kSel1Points)
   int tile_scorer = DLG_TILE_EXACT;  // pruned plane scorer (spatial.hpp kTileScorer*)
-  bool nbr_fused = true;          // PCL-float radius normals in one fused pass (else chunked)
-  bool bfs_wave = true;           // RegulateNormal's claim pass: one wave per frontier node
+  int nbr_fused = 1;           // PCL-float radius normals in one fused pass (else chunked)
+  int bfs_wave = 1;            // RegulateNormal's claim pass: one wave per frontier node
   // PCL float refit (DLG_REFIT_PCL, any rank count): 1 = the nine sums on the device (fsum.hip,
   // exact), 0 = gathered to the host and summed there, 2 = device, and the host recomputes the
   // refit's tail from the published sums every round, 3 = as 2 and the round's select is always
@@ -180,20 +181,20 @@ struct PathOptions {
                        // 0 off, -1 = on when every rank holds the same cloud, ids included)
   int fs_protocol = 0;  // several ranks: the PCL refit's protocol (DLG_OPT_FS_ONE_WALK, 0..2)
   int fs_segments = 8;  // one rank: walkers per float chain (DLG_OPT_FS_SEGMENTS)
-  bool fs_poison = false;  // tests only: fill the float-sum walk's window tables with garbage
+  int fs_poison = 0;    // tests only: fill the float-sum walk's window tables with garbage
                            // entries stamped for the next launch before the clear (fs_reset)
   int fault_round = 0;     // tests only (DLG_OPT_FAULT_INJECT): > 0 = this rank throws in the
                            // middle of extract round fault_round - 1 (after the round's scoring)
-  bool sync_check = false; // DLG_OPT_SYNC_CHECK: per-round allgather of (round, inliers,
+  int sync_check = 0;   // DLG_OPT_SYNC_CHECK: per-round allgather of (round, inliers,
                            // coefficient bits, collectives issued), mismatch fails the call
   int sel1_ticket = -1;    // DLG_OPT_SEL1_TICKET: single-pass select tiles numbered by an atomic
                            // ticket (dispatch order) instead of the workgroup index: 1 always,
                            // 0 never, -1 while another context of this process shares the device
-  bool bounds_stream = false;  // DLG_OPT_BOUNDS_STREAM: lean rounds' survivor sphere bounds on a
+  int bounds_stream = 0;    // DLG_OPT_BOUNDS_STREAM: lean rounds' survivor sphere bounds on a
                                // second stream beside the list pass (event-ordered)
   int spatial_curve = 1;  // DLG_OPT_SPATIAL_CURVE: 1 Hilbert, 0 Morton order of the spatial copy
-  bool fs_join = true;    // DLG_OPT_FS_JOIN: segmented walk's joins by each chain's last walker
-  bool unrefined_list = true;  // DLG_OPT_UNREFINED_LIST: lean PCL refit's inliers by one list pass
+  int fs_join = 1;     // DLG_OPT_FS_JOIN: segmented walk's joins by each chain's last walker
+  int unrefined_list = 1;   // DLG_OPT_UNREFINED_LIST: lean PCL refit's inliers by one list pass
 };
 
 struct dlg_ctx {
@@ -236,7 +237,7 @@ struct dlg_ctx {
   PinBuf<int32_t> h_pos, h_res, h_tot;
   PinBuf<double> h_mom;
   PinBuf<int64_t> h_g64;
-  DevBuf<float4> small;    // winning plane + samples + refined plane (segment_impl)
+  DevBuf<float4> small;    // winning plane + samples + refined plane (segment.cpp)
   DevBuf<float4> np_cn;    // NORMAL_PLANE pruned scoring: the hypotheses' normalized normals
   DevBuf<uint16_t> lp;     // pruned scoring: per super-tile lists of near planes
   DevBuf<int32_t> lp_n;
@@ -345,7 +346,7 @@ struct dlg_cloud {
     return s.view(n_active);
   }
   int spare() const { return cur == 0 ? 1 : 0; }
-  // lean-list rounds (driver.cpp): the list buffer holds only pristine indices (in its gid
+  // lean-list rounds (segment.cpp): the list buffer holds only pristine indices (in its gid
   // field; x, y, z, normals stale) until a path that reads coordinates materialises it
   bool buf_lean[2] = {false, false};
   bool list_lean() const { return cur >= 0 && buf_lean[cur]; }

@@ -3,7 +3,7 @@ SURVEY.md §8(e) run by world_size CPU processes over torch.distributed `gloo`.
 
 Every rank drives the product's host controller (dialog_amd.RansacControl = dlg_sac_control_*,
 the replay dlg_extract_planes runs between its kernels) on the global active count, and issues
-exactly the collectives the library issues per GPU (driver.cpp), in the same order
+exactly the collectives the library issues per GPU (segment.cpp), in the same order
 and with the same types and sizes, with the oracle standing in for the device kernels (test
 infrastructure):
 
@@ -70,7 +70,7 @@ class Coll:
         return np.stack([o.numpy() for o in outs])
 
     def gather_lists(self, arr, width):
-        """driver.cpp gather_lists: counts by allgather_i64, then one padded allgather"""
+        """segment.cpp gather_lists: counts by allgather_i64, then one padded allgather"""
         cnt = self.allgather(np.array([arr.size // width], np.int64))[:, 0]
         m = int(cnt.max())
         if m == 0:
@@ -93,7 +93,7 @@ def _pcl_refit(O, xyz, coeff):
 
 
 def hyp_slice(D, rank, world):
-    """driver.cpp one_batch: this rank's hypotheses [lo, hi) under DLG_OPT_HYP_SHARD"""
+    """segment.cpp SegmentRound::score: this rank's hypotheses [lo, hi) under DLG_OPT_HYP_SHARD"""
     U = (D + 63) // 64
     return min(D, 64 * (U * rank // world)), min(D, 64 * (U * (rank + 1) // world))
 
@@ -132,7 +132,7 @@ def run(rank, world, port, out_dir, n_points, n_planes, threshold, max_planes, m
         if N < floor_n:
             break
         if refit == "fast" and qexp is None and world > 1 and not hyp_shard:
-            # the cloud's global quantum, before the first round's draws (driver.cpp segment_impl)
+            # the cloud's global quantum, before the first round's draws (segment.cpp SegmentRound::prepare)
             fin_pts = pts[mine_ids][np.isfinite(pts[mine_ids]).all(axis=1)]
             f = float(np.abs(fin_pts).max()) if fin_pts.size else 0.0
             qexp = int(np.frexp(cc.allreduce_max_f64(f))[1])

@@ -158,7 +158,7 @@ def test_hyp_sharded_extract_gloo(tmp_path, world, refit, batch):
 
 
 def test_hyp_slices_partition():
-    """The slices of driver.cpp one_batch / dist_protocol.hyp_slice partition [0, D) into whole
+    """The slices of segment.cpp SegmentRound::score / dist_protocol.hyp_slice partition [0, D) into whole
     64-hypothesis groups (an exhaustive kernel's padded group stays inside its rank's slice)."""
     from dist_protocol import hyp_slice
     for D in (1, 63, 64, 65, 100, 511, 4096, 4000):
