@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libdialog_amd.so")  # (A/B tooling rebinds it: tools/with_lib.py)
 
 DLG_OK = 0
+DLG_ERR_INVALID = 1
 DLG_ERR_INTERNAL = 6
 DLG_ERR_COMM = 4
 DLG_ERR_CAPACITY = 5
@@ -33,7 +34,7 @@ SYMBOLS = [
     "dlg_sac_control_result", "dlg_cloud_build_spatial", "dlg_ctx_set_option",
     "dlg_ctx_get_option", "dlg_prune_stats", "dlg_estimate_normals_ex", "dlg_cloud_drop_spatial",
     "dlg_abi_struct_size", "dlg_float_sums", "dlg_cloud_estimate_normals", "dlg_plane_border",
-    "dlg_cloud_regulate_normals", "dlg_shard_range",
+    "dlg_cloud_regulate_normals", "dlg_shard_range", "dlg_cloud_signature",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -151,6 +152,7 @@ def load():
     L.dlg_cloud_build_spatial.argtypes = [vp, vp]
     L.dlg_cloud_drop_spatial.argtypes = [vp]
     L.dlg_cloud_active.argtypes = [vp, i64p]
+    L.dlg_cloud_signature.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     L.dlg_sac_segment.argtypes = [vp, vp, C.POINTER(SacParams), fp, i32p, C.c_int64, i64p,
                                   C.POINTER(SacStats)]
     L.dlg_sac_segment_host.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,

@@ -246,7 +246,7 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   c->pos.release(); c->samples.release(); c->hyps.release(); c->res.release();
   c->tile_in.release(); c->tile_off_in.release(); c->tile_off_out.release(); c->totals.release();
   c->partials.release(); c->moments.release(); c->scratch_f64.release(); c->inl_gid.release(); c->inl_xyz.release();
-  c->small.release(); c->h_small.release();
+  c->small.release(); c->h_small.release(); c->sig.release();
   c->gath64.release(); c->gath32.release();
   c->h_pos.release(); c->h_res.release(); c->h_tot.release(); c->h_mom.release(); c->h_g64.release();
   c->h_stage.release();
@@ -437,6 +437,23 @@ dlg_status dlg_cloud_active(const dlg_cloud* cl, int64_t* n) {
   if (!cl || !n) return DLG_ERR_INVALID;
   *n = cl->n_active;
   return DLG_OK;
+}
+
+dlg_status dlg_cloud_signature(dlg_ctx* c, dlg_cloud* cl, uint64_t* out) {
+  if (!c || !cl || !out || cl->ctx != c) return DLG_ERR_INVALID;
+  return guarded(c, [&] {
+    if (!cl->sig_known) {  // one reduction per cloud, on demand: no upload pays for it
+      c->sig.ensure(1);
+      launch_signature(cl->pristine.view(cl->n_total), c->sig.p, c->stream);
+      HIPCHK(hipGetLastError());
+      uint64_t h = 0;
+      HIPCHK(hipMemcpyAsync(&h, c->sig.p, 8, hipMemcpyDeviceToHost, c->stream));
+      sync(c);
+      cl->sig = h;
+      cl->sig_known = true;
+    }
+    *out = cl->sig;
+  });
 }
 
 dlg_status dlg_cloud_set_normals(dlg_ctx* c, dlg_cloud* cl, const float* normals, int64_t n,

@@ -230,6 +230,7 @@ struct dlg_ctx {
   DevBuf<unsigned> pick_done;          // the fused pick's workgroup ticket (zero between launches)
   DevBuf<unsigned> mom_done;           // k_moments' last-workgroup counter (zero between launches)
   DevBuf<double> scratch_f64;          // max-allreduce of host doubles
+  DevBuf<uint64_t> sig;                // dlg_cloud_signature's result word
   DevBuf<int32_t> inl_gid;
   DevBuf<float> inl_xyz;
   DevBuf<int64_t> gath64;
@@ -313,6 +314,10 @@ struct dlg_cloud {
   bool gid_ident = false;  // pristine gid[i] == id_base + i (uploaded without setIndices)
   bool repl_known = false, repl = false;  // several ranks: every rank holds this same cloud
                                           // (decided at the first call, hyp_shard_on)
+  // content signature of the pristine list (k_signature), computed at the first
+  // dlg_cloud_signature and kept (the pristine list never changes)
+  bool sig_known = false;
+  uint64_t sig = 0;
   bool has_normals = false;
   // the attached normals as given (PCL's normal_x/y/z and curvature, pristine order): RegulateNormal
   // on the device copy (dlg_cloud_regulate_normals) flips these and re-derives the normalised ones

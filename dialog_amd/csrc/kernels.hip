@@ -1454,6 +1454,20 @@ __global__ void k_absmax(PointsView src, uint32_t* __restrict__ out4) {
   }
 }
 
+// dlg_cloud_signature: the wrapping 64-bit sum over the list of point_signature (kernels.hpp) of
+// each point's position and x, y, z, gid bit patterns.  A sum, so grid size, wave order and the
+// order of the atomics do not matter: per-thread accumulators, a wave reduction, one atomic a wave
+__global__ void k_signature(PointsView src, unsigned long long* __restrict__ out) {
+  unsigned long long acc = 0ull;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < src.n; e += stride)
+    acc += point_signature((uint64_t)e, __float_as_uint(src.x[e]), __float_as_uint(src.y[e]),
+                           __float_as_uint(src.z[e]), (uint32_t)src.gid[e]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+  if ((threadIdx.x & (kWave - 1)) == 0 && acc) atomicAdd(out, acc);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1830,6 +1844,15 @@ void launch_absmax(PointsView src, uint32_t* out4, hipStream_t s) {
   unsigned g = cdiv(src.n, 256);
   if (g > 1024) g = 1024;
   hipLaunchKernelGGL(k_absmax, dim3(g), dim3(256), 0, s, src, out4);
+}
+
+void launch_signature(PointsView src, uint64_t* out, hipStream_t s) {
+  (void)hipMemsetAsync(out, 0, sizeof(uint64_t), s);
+  if (src.n <= 0) return;
+  unsigned g = cdiv(src.n, 256);
+  if (g > 1024) g = 1024;
+  hipLaunchKernelGGL(k_signature, dim3(g), dim3(256), 0, s, src,
+                     reinterpret_cast<unsigned long long*>(out));
 }
 
 }  // namespace dlg

@@ -305,4 +305,23 @@ void launch_upload_gather(const float* raw, int64_t stride_f, const int32_t* idx
 // largest |coordinate| of its finite points (fast refit quantum); out: 4 floats (as uint bits)
 void launch_absmax(PointsView src, uint32_t* out4, hipStream_t s);
 
+// Content signature of a point list (dlg_cloud_signature): the wrapping 64-bit sum over the list
+// of point_signature(position, x bits, y bits, z bits, gid bits).  For a fixed position the hash
+// is a bijection of (x, y) and of (z, gid) -- xors, odd multiplications and xor-shifts -- so any
+// change of one point's bits (-0.0 for +0.0, a NaN payload, one mantissa bit) changes its term
+// and with it the sum; the position term makes the sum depend on the order of the list.
+__host__ __device__ inline uint64_t point_signature(uint64_t pos, uint32_t xb, uint32_t yb,
+                                                    uint32_t zb, uint32_t gb) {
+  uint64_t h = (pos + 1) * 0x9E3779B97F4A7C15ull;
+  h ^= (uint64_t)xb | ((uint64_t)yb << 32);
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 29;
+  h ^= (uint64_t)zb | ((uint64_t)gb << 32);
+  h *= 0x94D049BB133111EBull;
+  h ^= h >> 32;
+  return h;
+}
+// *out (device, one word) = the signature of src; stream-ordered, 0 for an empty list
+void launch_signature(PointsView src, uint64_t* out, hipStream_t s);
+
 }  // namespace dlg

@@ -234,6 +234,13 @@ class Cloud:
             _f32p(out) if copy_out else None, 16))
         return proc[:n].astype(bool), int(cnt.value), out
 
+    def signature(self) -> int:
+        """dlg_cloud_signature: the 64-bit content signature of the cloud as uploaded (every
+        coordinate bit and id, in list order)."""
+        v = C.c_uint64()
+        self.ctx.check(self.ctx._L.dlg_cloud_signature(self.ctx.h, self.h, C.byref(v)))
+        return v.value
+
     @property
     def n_active(self):
         v = C.c_int64()

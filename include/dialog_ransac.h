@@ -44,7 +44,8 @@ extern "C" {
  * 5: a failing rank aborts its group (peers return DLG_ERR_COMM); DLG_OPT_FAULT_INJECT,
  * DLG_OPT_SYNC_CHECK, DLG_OPT_COMM_TIMEOUT_MS, DLG_OPT_SEL1_TICKET, DLG_OPT_BOUNDS_STREAM;
  * DLG_OPT_SPATIAL_CURVE, DLG_OPT_FS_JOIN, DLG_OPT_UNREFINED_LIST (same ABI version: added options);
- * DLG_OPT_HYP_SHARD defaults to -1 (automatic); dlg_shard_range */
+ * DLG_OPT_HYP_SHARD defaults to -1 (automatic); dlg_shard_range; dlg_cloud_signature (same ABI
+ * version: an added entry) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -182,6 +183,17 @@ dlg_status dlg_cloud_build_spatial(dlg_ctx* ctx, dlg_cloud* cloud);
  * points. */
 dlg_status dlg_cloud_drop_spatial(dlg_cloud* cloud);
 dlg_status dlg_cloud_active(const dlg_cloud* cloud, int64_t* n_active_local);
+/* Content signature of the cloud as uploaded (every point, whatever has been extracted since):
+ * the sum modulo 2^64 over list positions i = 0..n-1 of h(i, x, y, z, id), where x, y, z are the
+ * point's float bit patterns (-0.0 differs from +0.0, NaN payloads count), id its global id, and
+ *   h = (i + 1) * 0x9E3779B97F4A7C15;  h ^= x | y << 32;   h *= 0xBF58476D1CE4E5B9;  h ^= h >> 29;
+ *   h ^= z | id << 32;  h *= 0x94D049BB133111EB;  h ^= h >> 32        (64-bit, wrapping)
+ * so any changed bit of one point and (up to a 2^-64 coincidence) any reordering change it; 0 for
+ * an empty cloud.  Two ranks hold the same cloud exactly when their counts, id_base and
+ * signatures agree.  One reduction on the device, run at the first request and kept; nothing
+ * else computes it (DLG_OPT_HYP_SHARD's automatic decision does not read it yet: see its
+ * comment). */
+dlg_status dlg_cloud_signature(dlg_ctx* ctx, dlg_cloud* cloud, uint64_t* signature_out);
 /* SACSegmentationFromNormals::setInputNormals: one normal record per uploaded point (n = the
  * dlg_points n of dlg_cloud_upload; the cloud's indices select from it like from the points).
  * stride_bytes 16 = (nx, ny, nz, curvature), >= 32 = pcl::Normal (curvature at byte 16).
@@ -473,7 +485,11 @@ enum {
                                0: point sharding (each rank uploads its shard).  -1 (default):
                                hypothesis sharding exactly when every rank holds the same cloud
                                (same ids and extent), decided once per cloud -- the layout
-                               dlg_shard_range hands out when point shards would be too small */
+                               dlg_shard_range hands out when point shards would be too small.
+                               The decision compares counts, id_base and extents, not the
+                               points: ranks that upload different points with equal counts,
+                               id_base and extents (index subsets of an axis-aligned scene)
+                               must set 0 themselves, and every rank must set the same value */
   DLG_OPT_FS_ONE_WALK = 14, /* several ranks, PCL float refit (same sums every way): 0 (default)
                                = walk, rebase every rank on the guess the walks propagate, walk
                                again, then hand the exact chain ends rank to rank (each repair a
