@@ -173,9 +173,11 @@ __global__ void k_gather_build(const int32_t* pos, int D, int Dp, PointsView src
 constexpr int kScBS = 512;  // 8 waves share one LDS copy of the hypotheses
 constexpr int kHT = 1024;
 
-// the exact VALU kernel (PCL op order for every test): the reference the matrix-core and pruned
-// kernels are checked against (tests/test_score_variants.py), and the scorer of contexts with
-// DLG_OPT_SCORE_KERNEL = DLG_SCORE_EXACT
+// the exact VALU kernel (PCL op order for every test), the scorer of contexts with
+// DLG_OPT_SCORE_KERNEL = DLG_SCORE_EXACT.  The reference of every scorer's counts, this one's
+// included, is the oracle's countWithinDistance (tests/test_score_counts_oracle.py); the A/B-only
+// tile scorers are compared with this kernel (tests/test_score_variants.py) and so pinned to the
+// oracle through it
 template <int P>
 __global__ __launch_bounds__(kScBS) void k_score(const float* __restrict__ X,
                                                  const float* __restrict__ Y,

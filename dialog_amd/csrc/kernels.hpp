@@ -61,8 +61,9 @@ constexpr int kMaxHypPerLaunch = 4096;  // LDS count array of the scoring kernel
 constexpr int kSelTile = 4096;          // points per select/compact workgroup
 
 // Exhaustive scoring kernels (every active point against every hypothesis; the pruned kernel
-// of spatial.hpp is the default whenever the cloud has a Morton copy).  All give bit-identical
-// counts (tests/test_score_variants.py); dlg_score_benchmark takes these values.
+// of spatial.hpp is the default whenever the cloud has a Morton copy).  All give the counts of
+// the oracle's countWithinDistance, the reference (tests/test_score_counts_oracle.py), and so
+// bit-identical counts (tests/test_score_variants.py); dlg_score_benchmark takes these values.
 //   exact  : PCL op order (3 mul + 3 add) + compare on the VALU, 4 points per lane
 //   bf16   : plane distances on the bf16 matrix cores (3-way split operands, products exact),
 //            counting + band tracking on the VALU, exact PCL re-decision inside the rounding band

@@ -416,7 +416,16 @@ dlg_status dlg_synchronize(dlg_ctx* ctx);
 /* Scoring-kernel micro-benchmark (kernel A/B on the device): D random plane hypotheses through
  * the same gather/build path, `kernel` (DLG_SCORE_EXACT, DLG_SCORE_BF16 or DLG_SCORE_PRUNED, the
  * last needing the cloud's Morton copy) launched `reps` times on the cloud's active points;
- * returns the mean device time per launch and (optional) the counts of the last launch. */
+ * returns the mean device time per launch and (optional) the counts of the last launch.
+ * The draw is fixed, so that a host can replay the hypotheses and check counts_out against
+ * PCL's countWithinDistance (tests/test_score_counts_oracle.py): one Mt19937 seeded with 777,
+ * rnd() = next() >> 1 as in dlg_sac_control; position i of the 3 * D is (uint32_t)rnd() %
+ * n_active, an index into the cloud's active list in list order, three consecutive positions
+ * per hypothesis (repeats are not redrawn).  List entry `pos` is point pos of an unindexed cloud
+ * as uploaded, point indices[pos] of a cloud uploaded with indices, and after extraction rounds
+ * entry pos of the remaining list, which keeps the uploaded order.  counts_out[d] is the number
+ * of active points within `threshold` of hypothesis d's plane, 0 when isSampleGood rejects its
+ * sample; needs >= 3 active points and 1 <= D <= 4096. */
 dlg_status dlg_score_benchmark(dlg_ctx* ctx, dlg_cloud* cloud, int D, int kernel, int reps,
                                double threshold, double* ms_per_launch, int32_t* counts_out);
 /* DLG_REFIT_PCL's device refit (fsum.hip) on caller data, for tests and measurement: the nine
