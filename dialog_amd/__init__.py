@@ -8,7 +8,9 @@ fallback: without the library or a gfx950 device every compute call raises.
 from .sac import (SAC_RANSAC, SACMODEL_NORMAL_PLANE, SACMODEL_PLANE, Cloud, Context,  # noqa: F401
                   RansacControl,
                   DialogError, SACSegmentation, SACSegmentationFromNormals, extract_planes,
-                  make_params, segment_cloud, shard_range)
+                  make_params, segment_cloud, shard_range,
+                  SACMODEL_PERPENDICULAR_PLANE, SACMODEL_PARALLEL_PLANE, score_samples,
+                  axis_verdicts)
 from .normals import (NormalEstimation, estimate_normals, orient_normals_nn,  # noqa: F401
                       regulate_normals)
 from .preprocess import preprocess, remove_redundant_points  # noqa: F401
@@ -28,4 +30,5 @@ __all__ = ["Context", "Cloud", "SACSegmentation", "extract_planes", "segment_clo
            "DLG_REFIT_FAST", "DialogError", "LIB_PATH", "NormalEstimation", "estimate_normals",
            "regulate_normals", "SACSegmentationFromNormals", "orient_normals_nn",
            "preprocess", "remove_redundant_points", "PostProcessParams", "post_process_planes",
-           "refit_planes", "cluster_filter", "RansacControl"]
+           "refit_planes", "cluster_filter", "RansacControl", "SACMODEL_PERPENDICULAR_PLANE",
+           "SACMODEL_PARALLEL_PLANE", "score_samples"]

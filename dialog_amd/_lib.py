@@ -17,6 +17,8 @@ DLG_ERR_COMM = 4
 DLG_ERR_CAPACITY = 5
 DLG_SACMODEL_PLANE = 0
 DLG_SACMODEL_NORMAL_PLANE = 11
+DLG_SACMODEL_PERPENDICULAR_PLANE = 9
+DLG_SACMODEL_PARALLEL_PLANE = 15
 DLG_REFIT_PCL = 0
 DLG_REFIT_FAST = 1
 ABI_VERSION = 5  # include/dialog_ransac.h DLG_ABI_VERSION: the structs below match that header
@@ -35,6 +37,7 @@ SYMBOLS = [
     "dlg_ctx_get_option", "dlg_prune_stats", "dlg_estimate_normals_ex", "dlg_cloud_drop_spatial",
     "dlg_abi_struct_size", "dlg_float_sums", "dlg_cloud_estimate_normals", "dlg_plane_border",
     "dlg_cloud_regulate_normals", "dlg_shard_range", "dlg_cloud_signature",
+    "dlg_ctx_set_axis", "dlg_ctx_get_axis", "dlg_score_samples", "dlg_axis_verdicts",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -198,6 +201,11 @@ def load():
     L.dlg_post_process_planes.argtypes = [vp, C.POINTER(Points), C.POINTER(Planes),
                                           C.POINTER(PostProcessParams), fp, i64p, i32p, C.c_int64,
                                           i32p, C.c_int64, i64p]
+    L.dlg_ctx_set_axis.argtypes = [vp, fp, C.c_double]
+    L.dlg_ctx_get_axis.argtypes = [vp, fp, C.POINTER(C.c_double)]
+    L.dlg_score_samples.argtypes = [vp, vp, C.POINTER(SacParams), i32p, C.c_int, i32p, i32p, i32p,
+                                    fp]
+    L.dlg_axis_verdicts.argtypes = [C.c_int, C.c_double, fp, C.c_int64, i32p, i32p, fp]
     L.dlg_cluster_filter.argtypes = [vp, C.POINTER(Points), C.c_float, C.c_int32, i32p,
                                      C.c_int64, i64p]
     for s in SYMBOLS:

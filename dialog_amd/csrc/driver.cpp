@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <climits>
 #include <cstdio>
 #include <cstring>
@@ -630,6 +631,56 @@ dlg_status dlg_extract_planes(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params* p
   c->sp_check = false;
   xs->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return s;
+}
+
+dlg_status dlg_ctx_set_axis(dlg_ctx* c, const float axis[3], double eps_angle) {
+  if (!c || !axis) return DLG_ERR_INVALID;
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(axis[k])) return fail(c, DLG_ERR_INVALID, "axis component is NaN or infinite");
+  if (eps_angle != eps_angle) return fail(c, DLG_ERR_INVALID, "eps_angle is NaN");
+  std::memcpy(c->axis, axis, sizeof(c->axis));
+  c->eps_angle = eps_angle;
+  return DLG_OK;
+}
+
+dlg_status dlg_ctx_get_axis(const dlg_ctx* c, float axis[3], double* eps_angle) {
+  if (!c || !axis || !eps_angle) return DLG_ERR_INVALID;
+  std::memcpy(axis, c->axis, sizeof(c->axis));
+  *eps_angle = c->eps_angle;
+  return DLG_OK;
+}
+
+dlg_status dlg_score_samples(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params* prm,
+                             const int32_t* positions, int n_draws, int32_t* counts_out,
+                             int32_t* good_out, int32_t* valid_out, float* coeffs_out) {
+  if (!c || !cl || !prm || !positions || !counts_out || !good_out || cl->ctx != c)
+    return DLG_ERR_INVALID;
+  if (n_draws < 1 || n_draws > kMaxHypPerLaunch) return fail(c, DLG_ERR_INVALID, "n_draws: 1..4096");
+  return guarded_group(c, [&] {
+    HypShardScope hs(c, hyp_shard_on(c, cl));
+    score_samples(c, cl, *prm, positions, n_draws, counts_out, good_out, valid_out, coeffs_out);
+  });
+}
+
+dlg_status dlg_axis_verdicts(int model, double eps_angle, const float* f, int64_t n,
+                             int32_t* by_threshold, int32_t* by_formula, float thresholds[2]) {
+  if ((model != DLG_SACMODEL_PERPENDICULAR_PLANE && model != DLG_SACMODEL_PARALLEL_PLANE) ||
+      n < 0 || (n > 0 && (!f || !by_threshold || !by_formula)) || eps_angle != eps_angle)
+    return DLG_ERR_INVALID;
+  const float unit[3] = {0.0f, 0.0f, 1.0f};
+  const AxisTest t = make_axis_test(model, unit, eps_angle);
+  if (thresholds) {
+    thresholds[0] = t.t_lo;
+    thresholds[1] = t.t_hi;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    by_threshold[i] = t.mode == kAxisNone || axis_verdict(t, f[i]) ? 1 : 0;
+    by_formula[i] = !(eps_angle > 0.0) ? 1
+                    : model == DLG_SACMODEL_PERPENDICULAR_PLANE
+                        ? (perpendicular_valid_direct(f[i], eps_angle) ? 1 : 0)
+                        : (parallel_valid_direct(f[i], eps_angle) ? 1 : 0);
+  }
+  return DLG_OK;
 }
 
 dlg_status dlg_float_sums(dlg_ctx* c, const float* xyz, int64_t n, const float cin[4], int reps,

@@ -215,6 +215,10 @@ struct dlg_ctx {
   bool profiling = false;
   bool walk_events = false;  // (profiling level 1: the PCL refit walk's events too)
   bool sp_all = true;  // every rank holds a valid spatial copy (agreed per extraction)
+  // dlg_ctx_set_axis: setAxis / setEpsAngle of the axis-constrained plane models (read whenever
+  // the model is SACMODEL_PERPENDICULAR_PLANE or SACMODEL_PARALLEL_PLANE; axis_model.hpp)
+  float axis[3] = {0.0f, 0.0f, 0.0f};
+  double eps_angle = 0.0;
   // scratch
   DevBuf<int32_t> pos;
   DevBuf<SampleRec> samples;

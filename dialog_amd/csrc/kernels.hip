@@ -36,6 +36,17 @@ __device__ __forceinline__ bool model_in(const PointsView& src, int64_t e, float
   return fabsf(pcl_dot(cf.x, cf.y, cf.z, cf.w, x, y, z)) < mt.cthr;
 }
 
+// the plane a select / moments kernel tests its points against: the given one, or -- an axis-
+// constrained model whose isModelValid rejects it (cn = its normalized4) -- a NaN plane, which no
+// point is within any distance of (selectWithinDistance of an invalid model returns nothing)
+__device__ __forceinline__ float4 plane_or_nan(float4 cf, float4 cn, const ModelTest& mt) {
+  if (mt.axis.mode != kAxisNone && !axis_valid_n(mt.axis, cn.x, cn.y, cn.z)) {
+    const float q = __builtin_nanf("");
+    return make_float4(q, q, q, q);
+  }
+  return cf;
+}
+
 // ---------------------------------------------------------------------------------------------
 // lidx (lean lists): the list holds pristine indices only; src = the pristine copy, n_list the
 // list length
@@ -58,27 +69,18 @@ __global__ void k_gather_samples(const int32_t* __restrict__ pos, int m, int64_t
 // isSampleGood + computeModelCoefficients of one draw, in PCL's op order
 __device__ __forceinline__ HypRec build_hyp(const SampleRec s0, const SampleRec s1,
                                             const SampleRec s2, float cthr, float ax, float ay,
-                                            float az) {
-  float a0 = s1.x - s0.x, a1 = s1.y - s0.y, a2 = s1.z - s0.z;
-  float b0 = s2.x - s0.x, b1 = s2.y - s0.y, b2 = s2.z - s0.z;
-  float r0 = a0 / b0, r1 = a1 / b1, r2 = a2 / b2;
-  bool good = (r0 != r1) || (r2 != r1);
+                                            float az, const AxisTest& axis) {
+  const float p0[3] = {s0.x, s0.y, s0.z}, p1[3] = {s1.x, s1.y, s1.z}, p2[3] = {s2.x, s2.y, s2.z};
+  float cf[4];
+  const bool good = sample_plane(p0, p1, p2, cf);
   HypRec h;
   h.w = 0.0f;
   h.good = good ? 1 : 0;
-  if (good) {
-    float c0 = a1 * b2 - a2 * b1;
-    float c1 = a2 * b0 - a0 * b2;
-    float c2 = a0 * b1 - a1 * b0;
-    float c3 = 0.0f;
-    // VectorXf::normalize(): Eigen 3.3 guards z > 0; squaredNorm = (c0^2 + c2^2) + (c1^2 + c3^2)
-    float z = (c0 * c0 + c2 * c2) + (c1 * c1 + c3 * c3);
-    if (z > 0.0f) {
-      float sq = sqrtf(z);  // correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt)
-      c0 = c0 / sq; c1 = c1 / sq; c2 = c2 / sq; c3 = c3 / sq;
-    }
-    float dot = (c0 * s0.x + c2 * s0.z) + (c1 * s0.y + c3 * 1.0f);
-    h.a = c0; h.b = c1; h.c = c2; h.d = -1.0f * dot;
+  // an axis-constrained model's isModelValid (wave-uniform switch): an invalid hypothesis is an
+  // ordinary good draw that counts nothing -- a NaN plane to every scorer
+  const bool valid = axis.mode == kAxisNone || !good || axis_valid(axis, cf[0], cf[1], cf[2]);
+  if (good && valid) {
+    h.a = cf[0]; h.b = cf[1]; h.c = cf[2]; h.d = cf[3];
     // prefilter band: |pcl_dot - fma_chain| <= 7 u S, S = sum |coef_k * coord_k|, u = 2^-24
     double S = fabs((double)h.a) * ax + fabs((double)h.b) * ay + fabs((double)h.c) * az +
                fabs((double)h.d);
@@ -88,6 +90,7 @@ __device__ __forceinline__ HypRec build_hyp(const SampleRec s0, const SampleRec 
     // min3 variant: r = fl(|f| - cthr) carries <= 2^-24 |r| relative error on top of E
     h.w = __double2float_ru(E * (1.0 + 1e-4));
   } else {
+    if (!valid) h.good |= kHypInvalid;
     h.a = h.b = h.c = h.d = __builtin_nanf("");
     h.tlo = h.thi = h.w = 0.0f;
   }
@@ -103,7 +106,7 @@ __device__ __forceinline__ HypRec nan_hyp() {  // padding / not a plane: counts 
 }
 
 __global__ void k_build_hyps(const SampleRec* __restrict__ s, int D, int Dp, float cthr, float ax,
-                             float ay, float az, HypRec* __restrict__ hyps,
+                             float ay, float az, AxisTest axis, HypRec* __restrict__ hyps,
                              int32_t* __restrict__ good_out) {
   int d = blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= Dp) return;
@@ -111,7 +114,7 @@ __global__ void k_build_hyps(const SampleRec* __restrict__ s, int D, int Dp, flo
     hyps[d] = nan_hyp();
     return;
   }
-  const HypRec h = build_hyp(s[3 * d], s[3 * d + 1], s[3 * d + 2], cthr, ax, ay, az);
+  const HypRec h = build_hyp(s[3 * d], s[3 * d + 1], s[3 * d + 2], cthr, ax, ay, az, axis);
   hyps[d] = h;
   good_out[d] = h.good;
 }
@@ -121,7 +124,8 @@ __global__ void k_build_hyps(const SampleRec* __restrict__ s, int D, int Dp, flo
 __global__ void k_gather_build(const int32_t* pos, int D, int Dp, PointsView src,
                                const int32_t* __restrict__ lidx, int64_t n_list,
                                SampleRec* __restrict__ samples, float cthr, float ax, float ay,
-                               float az, HypRec* __restrict__ hyps, int32_t* __restrict__ res) {
+                               float az, AxisTest axis, HypRec* __restrict__ hyps,
+                               int32_t* __restrict__ res) {
   const int d = blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= Dp) return;
   res[d] = 0;  // counts[Dp]
@@ -155,7 +159,7 @@ __global__ void k_gather_build(const int32_t* pos, int D, int Dp, PointsView src
   }
 #pragma unroll
   for (int i = 0; i < 3; ++i) samples[3 * d + i] = r[i];
-  const HypRec h = build_hyp(r[0], r[1], r[2], cthr, ax, ay, az);
+  const HypRec h = build_hyp(r[0], r[1], r[2], cthr, ax, ay, az, axis);
   hyps[d] = h;
   res[Dp + d] = h.good;  // good[D]
 }
@@ -540,8 +544,8 @@ __global__ __launch_bounds__(kMoBS) void k_moments(PointsView src, const float4*
                                                    unsigned* __restrict__ done,
                                                    int64_t* __restrict__ out, int qexp,
                                                    float4* __restrict__ cout) {
-  const float4 cf = *cfp;
-  const float4 cn = eigen_normalized3(cf.x, cf.y, cf.z, 0.0f);
+  const float4 cn = eigen_normalized3(cfp->x, cfp->y, cfp->z, 0.0f);
+  const float4 cf = plane_or_nan(*cfp, cn, mt);
   int64_t acc[kMomDigits];
 #pragma unroll
   for (int k = 0; k < kMomDigits; ++k) acc[k] = 0;
@@ -583,8 +587,8 @@ __global__ __launch_bounds__(kMoBS) void k_moments_sp(PointsView src,
                                                       unsigned* __restrict__ done,
                                                       int64_t* __restrict__ out, int qexp,
                                                       float4* __restrict__ cout) {
-  const float4 cf = *cfp;
-  const float4 cn = eigen_normalized3(cf.x, cf.y, cf.z, 0.0f);
+  const float4 cn = eigen_normalized3(cfp->x, cfp->y, cfp->z, 0.0f);
+  const float4 cf = plane_or_nan(*cfp, cn, mt);
   int64_t acc[kMomDigits];
 #pragma unroll
   for (int k = 0; k < kMomDigits; ++k) acc[k] = 0;
@@ -701,8 +705,8 @@ __global__ __launch_bounds__(kSelBS) void k_select_count(PointsView src,
                                                          const float4* __restrict__ cfp,
                                                          ModelTest mt,
                                                          int32_t* __restrict__ tile_in) {
-  const float4 cf = *cfp;
-  const float4 cn = eigen_normalized3(cf.x, cf.y, cf.z, 0.0f);
+  const float4 cn = eigen_normalized3(cfp->x, cfp->y, cfp->z, 0.0f);
+  const float4 cf = plane_or_nan(*cfp, cn, mt);
   __shared__ int s_w[kSelBS / kWave];
   const int64_t base = (int64_t)blockIdx.x * kSelTile;
   int cnt = 0;
@@ -773,8 +777,8 @@ __global__ __launch_bounds__(kSelBS) void k_select_scatter(PointsView src,
                                                            float* __restrict__ inl_xyz,
                                                            PointsOut dst, int compact) {
   __shared__ int s_w[2][2][kSelBS / kWave];  // [buffer][in/out][wave]
-  const float4 cf = *cfp;
-  const float4 cn = eigen_normalized3(cf.x, cf.y, cf.z, 0.0f);
+  const float4 cn = eigen_normalized3(cfp->x, cfp->y, cfp->z, 0.0f);
+  const float4 cf = plane_or_nan(*cfp, cn, mt);
   const int64_t base = (int64_t)blockIdx.x * kSelTile;
   const int w = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
   int run_in = off_in[blockIdx.x], run_out = off_out[blockIdx.x];
@@ -998,8 +1002,8 @@ __global__ __launch_bounds__(kS1BS) void k_sel1_morton(PointsView src, const flo
   constexpr int kS1Slots = S1<kS1BS>::kSlots, kS1Tile = S1<kS1BS>::kTile;
   __shared__ int s_cnt[kS1Slots], s_pre[kS1Slots], s_base[2];
   const int tile = sel1_tile_of(L, s_base);
-  const float4 cf = *cfp;
-  const float4 cn = eigen_normalized3(cf.x, cf.y, cf.z, 0.0f);
+  const float4 cn = eigen_normalized3(cfp->x, cfp->y, cfp->z, 0.0f);
+  const float4 cf = plane_or_nan(*cfp, cn, mt);
   const int w = threadIdx.x / kWave;
   const int64_t base = (int64_t)tile * kS1Tile;
   float x[kS1It], y[kS1It], z[kS1It];
@@ -1123,8 +1127,8 @@ __global__ __launch_bounds__(kS1BS) void k_ulist(const int32_t* __restrict__ lid
   constexpr int kS1Slots = S1<kS1BS>::kSlots, kS1Tile = S1<kS1BS>::kTile;
   __shared__ int s_cnt[kS1Slots], s_pre[kS1Slots], s_base[2];
   const int tile = sel1_tile_of(L, s_base);
-  const float4 cf = *cfp;
-  const float4 cn = eigen_normalized3(cf.x, cf.y, cf.z, 0.0f);
+  const float4 cn = eigen_normalized3(cfp->x, cfp->y, cfp->z, 0.0f);
+  const float4 cf = plane_or_nan(*cfp, cn, mt);
   const int w = threadIdx.x / kWave;
   const int64_t base = (int64_t)tile * kS1Tile;
   int32_t p[kS1It];
@@ -1191,8 +1195,8 @@ __global__ __launch_bounds__(kMoBS) void k_ustamp(PointsView src, const float4* 
                                                   const float4* __restrict__ supers, float margin,
                                                   const float4* __restrict__ cfp, ModelTest mt,
                                                   uint32_t* __restrict__ bits) {
-  const float4 cf = *cfp;
-  const float4 cn = eigen_normalized3(cf.x, cf.y, cf.z, 0.0f);
+  const float4 cn = eigen_normalized3(cfp->x, cfp->y, cfp->z, 0.0f);
+  const float4 cf = plane_or_nan(*cfp, cn, mt);
   const int64_t nsup = (src.n + kSuperP - 1) / kSuperP, ntile = (src.n + kTileP - 1) / kTileP;
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t W = (int64_t)gridDim.x * (kMoBS / kWave);
@@ -1484,11 +1488,13 @@ void launch_gather_samples(const int32_t* pos, int m, int64_t lo, PointsView src
 
 void launch_gather_build(const int32_t* pos_host, int D, PointsView src, SampleRec* samples,
                          float cthr, float ax, float ay, float az, HypRec* hyps, int32_t* res,
-                         hipStream_t s, const int32_t* lidx, int64_t n_list) {
+                         hipStream_t s, const int32_t* lidx, int64_t n_list,
+                         const AxisTest* axis) {
   if (D <= 0) return;
   const int Dp = (D + 63) / 64 * 64;
   hipLaunchKernelGGL(k_gather_build, dim3(cdiv(Dp, 256)), dim3(256), 0, s, pos_host, D, Dp, src,
-                     lidx, lidx ? n_list : src.n, samples, cthr, ax, ay, az, hyps, res);
+                     lidx, lidx ? n_list : src.n, samples, cthr, ax, ay, az,
+                     axis ? *axis : AxisTest{}, hyps, res);
 }
 
 int sel1_tiles(int64_t n) { return (int)((n + kSel1Points[0] - 1) / kSel1Points[0]); }
@@ -1626,11 +1632,11 @@ void launch_ucompact(uint32_t* bits, int64_t nwords, PointsView pristine, Sel1St
 }
 
 void launch_build_hyps(const SampleRec* samples, int D, float cthr, float ax, float ay, float az,
-                       HypRec* hyps, int32_t* good, hipStream_t s) {
+                       HypRec* hyps, int32_t* good, hipStream_t s, const AxisTest* axis) {
   if (D <= 0) return;
   const int Dp = (D + 63) / 64 * 64;
   hipLaunchKernelGGL(k_build_hyps, dim3(cdiv(Dp, 256)), dim3(256), 0, s, samples, D, Dp, cthr, ax,
-                     ay, az, hyps, good);
+                     ay, az, axis ? *axis : AxisTest{}, hyps, good);
 }
 
 template <int P>

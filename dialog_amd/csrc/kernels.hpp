@@ -10,6 +10,7 @@
 
 #include <cstdint>
 
+#include "axis_model.hpp"
 #include "exact_refit.hpp"
 
 namespace dlg {
@@ -24,9 +25,13 @@ struct alignas(16) SampleRec {
 struct alignas(16) HypRec {
   float a, b, c, d;
   float tlo, thi;  // [cthr - 7 u S, cthr + 7 u S) rounded outwards
-  int32_t good;    // SampleConsensusModelPlane::isSampleGood
+  int32_t good;    // bit 0: SampleConsensusModelPlane::isSampleGood; bit 1 (kHypInvalid): an axis-
+                   // constrained model's isModelValid rejected it (its plane is NaN here: it counts
+                   // nothing; the real coefficients follow from its samples)
   float w;         // >= 7 u S (k_prep_bf16 derives the matrix-core band from it)
 };
+
+constexpr int32_t kHypInvalid = 2;
 
 // nrm (optional, SACMODEL_NORMAL_PLANE): per point (n.normalized() as Eigen computes it for
 // getAngle3D, curvature) -- normalised once at upload, bit-identical to normalising per test
@@ -50,11 +55,15 @@ struct PointsOut {
 // inlier test of the select / moments / scoring kernels
 //   SACMODEL_PLANE        : |pcl_dot(c, p)| < cthr            (cthr = smallest float >= threshold)
 //   SACMODEL_NORMAL_PLANE : |w d_normal + (1 - w) d_euclid| < thr, w = lambda (1 - curvature)
+//   SACMODEL_PERPENDICULAR_PLANE / SACMODEL_PARALLEL_PLANE: SACMODEL_PLANE's, and nothing at all
+//   when the plane fails isModelValid (axis: axis_model.hpp; every kernel that takes a plane
+//   with a ModelTest applies it to the plane it reads, so an invalid plane selects no point)
 struct ModelTest {
   float cthr;
   int normal_plane;
   double thr;
   double lambda;
+  AxisTest axis;
 };
 
 constexpr int kMaxHypPerLaunch = 4096;  // LDS count array of the scoring kernel
@@ -123,7 +132,8 @@ void launch_pick_p1(const PickArgs& a, hipStream_t s);
 // lidx: the lean list's pristine indices (src = the pristine copy, n_list = list length)
 void launch_gather_build(const int32_t* pos_host, int D, PointsView src, SampleRec* samples,
                          float cthr, float ax, float ay, float az, HypRec* hyps, int32_t* res,
-                         hipStream_t s, const int32_t* lidx = nullptr, int64_t n_list = 0);
+                         hipStream_t s, const int32_t* lidx = nullptr, int64_t n_list = 0,
+                         const AxisTest* axis = nullptr);
 
 // single-pass select (decoupled look-back) of the lean-list rounds: status words per tile, an
 // epoch per launch (so the words never need clearing)
@@ -158,8 +168,9 @@ void launch_sel1_list(const int32_t* lidx, int64_t n, const uint8_t* tag, uint8_
 // a lean list's x, y, z, gid (+ normals) from the pristine copy, in place (io.gid holds the
 // pristine indices on entry)
 void launch_list_materialize(PointsView pristine, int64_t n, const PointsOut& io, hipStream_t s);
+// axis (nullable): the axis-constrained models' isModelValid, applied to every good draw
 void launch_build_hyps(const SampleRec* samples, int D, float cthr, float ax, float ay, float az,
-                       HypRec* hyps, int32_t* good, hipStream_t s);
+                       HypRec* hyps, int32_t* good, hipStream_t s, const AxisTest* axis = nullptr);
 // counts[D] = #{i < n : |plane_h . (x_i, y_i, z_i, 1)| < cthr}, PCL (Eigen SSE) op order, with
 // kernel kScoreExact or kScoreBf16.  counts must be zeroed by the caller (same stream).
 void launch_score(PointsView src, const HypRec* hyps, int D, float cthr, int32_t* counts,

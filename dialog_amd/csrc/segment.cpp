@@ -42,6 +42,10 @@
 
 namespace dlg {
 
+static_assert(DLG_SACMODEL_PERPENDICULAR_PLANE == kModelPerpendicularPlane &&
+                  DLG_SACMODEL_PARALLEL_PLANE == kModelParallelPlane,
+              "axis_model.hpp's model values");
+
 bool trace_on() {
   static const bool on = [] {
     const char* e = std::getenv("DLG_TRACE");
@@ -475,7 +479,23 @@ RoundPlan make_plan(const dlg_ctx* c, const dlg_cloud* cl, const dlg_sac_params&
   p.mt.normal_plane = np ? 1 : 0;
   p.mt.thr = prm.threshold;
   p.mt.lambda = prm.normal_distance_weight;
+  // the axis-constrained plane models: SACMODEL_PLANE on every path, plus isModelValid as float
+  // thresholds (axis_model.hpp) in the hypothesis build and in every kernel that selects with a
+  // plane; kAxisNone for the other models and for eps <= 0
+  p.mt.axis = make_axis_test(prm.model, c->axis, c->eps_angle);
   return p;
+}
+
+// computeModelCoefficients of three kept samples (k_build_hyps' arithmetic, on the host)
+void sample_coefficients(const SampleRec* s, float c[4]) {
+  const float p0[3] = {s[0].x, s[0].y, s[0].z}, p1[3] = {s[1].x, s[1].y, s[1].z},
+              p2[3] = {s[2].x, s[2].y, s[2].z};
+  sample_plane(p0, p1, p2, c);
+}
+
+bool model_known(int model) {
+  return model == DLG_SACMODEL_PLANE || model == DLG_SACMODEL_NORMAL_PLANE ||
+         model == DLG_SACMODEL_PERPENDICULAR_PLANE || model == DLG_SACMODEL_PARALLEL_PLANE;
 }
 
 // one batch of draws on its way through the scoring
@@ -585,14 +605,22 @@ struct SegmentRound {
   }
 
   Batch draw_and_build() {
-    Batch b;
-    const int D = b.D = ctl.next_size();
+    const int D = ctl.next_size();
     // ---- host: drawIndexSample over positions
-    b.t_draw0 = trace_on() ? now_ms() : 0.0;
+    const double t_draw0 = trace_on() ? now_ms() : 0.0;
     c->h_pos.ensure(3 * (size_t)D);
+    ctl.next_batch(c->h_pos.p);
+    Batch b = build(D);
+    b.t_draw0 = t_draw0;
+    return b;
+  }
+
+  // the D draws whose list positions are in c->h_pos: samples, hypotheses, good flags
+  Batch build(int D) {
+    Batch b;
+    b.D = D;
     int32_t* hp = c->h_pos.p;
-    ctl.next_batch(hp);
-    b.t_draw1 = trace_on() ? now_ms() : 0.0;
+    b.t_draw0 = b.t_draw1 = trace_on() ? now_ms() : 0.0;
     // ---- device: gather, build, score
     c->pos.ensure(3 * (size_t)D);
     c->samples.ensure(3 * (size_t)D);
@@ -608,13 +636,13 @@ struct SegmentRound {
       // one launch: positions read from the pinned host buffer (the next round's draw rewrites
       // it only after this round's results were published, i.e. after this kernel ran)
       launch_gather_build(hp, D, pts, c->samples.p, P.cthr, am[0], am[1], am[2], c->hyps.p,
-                          c->res.p, c->stream, lidx, src.n);
+                          c->res.p, c->stream, lidx, src.n, &P.mt.axis);
     } else {
       HIPCHK(hipMemcpyAsync(c->pos.p, hp, 12 * (size_t)D, hipMemcpyHostToDevice, c->stream));
       launch_gather_samples(c->pos.p, 3 * D, offset, pts, c->samples.p, c->stream, lidx, src.n);
       c->comm->allreduce_sum(c->samples.p, 12 * (size_t)D, DType::I32, c->stream);
       launch_build_hyps(c->samples.p, D, P.cthr, am[0], am[1], am[2], c->hyps.p, c->res.p + Dp,
-                        c->stream);
+                        c->stream, &P.mt.axis);
       HIPCHK(hipMemsetAsync(c->res.p, 0, 4 * (size_t)Dp, c->stream));
     }
     return b;
@@ -1157,6 +1185,14 @@ struct SegmentRound {
     st->coeff_unrefined[2] = bh->c; st->coeff_unrefined[3] = bh->d;
     for (int i = 0; i < 3; ++i) st->best_sample[i] = bs[i].gid;
     out.coeff[0] = rc.x; out.coeff[1] = rc.y; out.coeff[2] = rc.z; out.coeff[3] = rc.w;
+    if (bh->good & kHypInvalid) {
+      // an axis-constrained model whose every hypothesis was invalid: the first good draw won
+      // with 0 inliers.  The device carried it as a NaN plane (no inliers, and the refit of
+      // fewer than 4 inliers keeps its input), so its real coefficients -- PCL reports them --
+      // are rebuilt from its samples with the arithmetic that built the hypothesis
+      sample_coefficients(bs, st->coeff_unrefined);
+      std::memcpy(out.coeff, st->coeff_unrefined, sizeof(out.coeff));
+    }
     out.has_model = true;
     out.n_in_local = c->h_tot.p[0];
     out.n_out_local = src.n == 0 ? 0 : c->h_tot.p[1];
@@ -1203,8 +1239,9 @@ SegOut segment_round(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params& prm, bool 
                      dlg_sac_stats* st, dlg_extract_stats* xs,
                      const std::vector<int64_t>* active_ranks) {
   std::memset(st, 0, sizeof(*st));
-  if (prm.model != DLG_SACMODEL_PLANE && prm.model != DLG_SACMODEL_NORMAL_PLANE)
-    throw DlgError(DLG_ERR_INVALID, "model must be SACMODEL_PLANE or SACMODEL_NORMAL_PLANE");
+  if (!model_known(prm.model))
+    throw DlgError(DLG_ERR_INVALID, "model must be SACMODEL_PLANE, SACMODEL_NORMAL_PLANE, "
+                                    "SACMODEL_PERPENDICULAR_PLANE or SACMODEL_PARALLEL_PLANE");
   if (prm.model == DLG_SACMODEL_NORMAL_PLANE && !cl->has_normals)  // PCL: "No input dataset containing normals was given!"
     throw DlgError(DLG_ERR_INVALID, "SACMODEL_NORMAL_PLANE needs normals (dlg_cloud_set_normals)");
   if (!(prm.threshold == prm.threshold)) throw DlgError(DLG_ERR_INVALID, "threshold is NaN");
@@ -1226,6 +1263,55 @@ SegOut segment_round(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params& prm, bool 
   return SegmentRound(c, cl, prm, compact, plan, N, std::move(per_rank), st, xs).run();
 }
 
+// dlg_score_samples: the round's own draw_and_build and score phases over the caller's draws
+// (3 list positions each), on the path make_plan chooses for this cloud -- every scorer, the
+// gather and count collectives of several ranks, the hypothesis slices -- with every draw's
+// verdicts and coefficients handed back instead of a decision.  The list is not changed.
+void score_samples(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params& prm, const int32_t* positions,
+                   int D, int32_t* counts_out, int32_t* good_out, int32_t* valid_out,
+                   float* coeffs_out) {
+  if (!model_known(prm.model)) throw DlgError(DLG_ERR_INVALID, "unknown model");
+  if (prm.model == DLG_SACMODEL_NORMAL_PLANE && !cl->has_normals)
+    throw DlgError(DLG_ERR_INVALID, "SACMODEL_NORMAL_PLANE needs normals (dlg_cloud_set_normals)");
+  if (!(prm.threshold == prm.threshold)) throw DlgError(DLG_ERR_INVALID, "threshold is NaN");
+  std::vector<int64_t> per_rank;
+  const int64_t N = allgather_i64(c, cl->n_active, &per_rank);
+  if (N > INT32_MAX) throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 active points");
+  if (N < 3) throw DlgError(DLG_ERR_INVALID, "need >= 3 active points");
+  for (int i = 0; i < 3 * D; ++i)
+    if (positions[i] < 0 || positions[i] >= N)
+      throw DlgError(DLG_ERR_INVALID, "position outside the active list");
+  const RoundPlan plan = make_plan(c, cl, prm, /*compact=*/false);
+  ensure_list_xyz(c, cl);
+  dlg_sac_stats st;
+  std::memset(&st, 0, sizeof(st));
+  SegmentRound r(c, cl, prm, false, plan, N, std::move(per_rank), &st, nullptr);
+  if (plan.pruned_any) ensure_sphere_bounds(c, cl);
+  c->h_pos.ensure(3 * (size_t)D);
+  std::memcpy(c->h_pos.p, positions, 12 * (size_t)D);
+  Batch b = r.build(D);
+  r.score(b, /*speculate=*/false);
+  std::vector<HypRec> hyps((size_t)D);
+  std::vector<SampleRec> smp(3 * (size_t)D);
+  HIPCHK(hipMemcpyAsync(c->h_res.p, c->res.p, 4 * ((size_t)b.Dp + D), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hyps.data(), c->hyps.p, sizeof(HypRec) * (size_t)D, hipMemcpyDeviceToHost,
+                        c->stream));
+  HIPCHK(hipMemcpyAsync(smp.data(), c->samples.p, sizeof(SampleRec) * 3 * (size_t)D,
+                        hipMemcpyDeviceToHost, c->stream));
+  sync(c);
+  for (int d = 0; d < D; ++d) {
+    const int32_t g = c->h_res.p[b.Dp + d];
+    const bool invalid = (g & kHypInvalid) != 0;
+    counts_out[d] = c->h_res.p[d];
+    good_out[d] = g != 0;
+    if (valid_out) valid_out[d] = invalid ? 0 : 1;
+    if (!coeffs_out) continue;
+    float* co = coeffs_out + 4 * (size_t)d;
+    co[0] = hyps[d].a; co[1] = hyps[d].b; co[2] = hyps[d].c; co[3] = hyps[d].d;
+    if (invalid) sample_coefficients(&smp[3 * (size_t)d], co);  // (the device's plane is NaN)
+  }
+}
+
 // an accepted extract round's removal: the spare buffers `so` was compacted into become current
 void commit_round(dlg_cloud* cl, const SegOut& so) {
   cl->buf_lean[cl->spare()] = so.lean;
@@ -1241,13 +1327,14 @@ void commit_round(dlg_cloud* cl, const SegOut& so) {
 }
 
 // DLG_OPT_SYNC_CHECK: every rank's view of the round just run -- (round, model, global inliers,
-// coefficient bits, collectives issued so far) -- allgathered and compared; the first rank that
-// differs from rank 0 fails the call on every rank (and, through guarded_group, nothing waits)
+// coefficient bits, collectives issued so far, the axis and eps_angle of dlg_ctx_set_axis) --
+// allgathered and compared; the first rank that differs from rank 0 fails the call on every rank
+// (and, through guarded_group, nothing waits)
 void check_in_step(dlg_ctx* c, int round, const SegOut& so) {
   Comm* g = c->group();
   const int W = g->world();
   if (W == 1) return;
-  constexpr int K = 5;
+  constexpr int K = 8;
   int64_t mine[K];
   uint32_t cb[4];
   std::memcpy(cb, so.coeff, sizeof(cb));
@@ -1256,6 +1343,12 @@ void check_in_step(dlg_ctx* c, int round, const SegOut& so) {
   mine[2] = (int64_t)(((uint64_t)cb[0] << 32) | cb[1]);
   mine[3] = (int64_t)(((uint64_t)cb[2] << 32) | cb[3]);
   mine[4] = (int64_t)g->ops();
+  // (the axis-constrained models' context state: every rank must have set the same values)
+  uint32_t ab[3];
+  std::memcpy(ab, c->axis, sizeof(ab));
+  mine[5] = (int64_t)(((uint64_t)ab[0] << 32) | ab[1]);
+  mine[6] = (int64_t)ab[2];
+  std::memcpy(&mine[7], &c->eps_angle, 8);
   c->gath64.ensure((size_t)K * (W + 1));
   c->h_g64.ensure((size_t)K * W);
   HIPCHK(hipMemcpyAsync(c->gath64.p + (size_t)K * W, mine, sizeof(mine), hipMemcpyHostToDevice,
@@ -1264,7 +1357,8 @@ void check_in_step(dlg_ctx* c, int round, const SegOut& so) {
   HIPCHK(hipMemcpyAsync(c->h_g64.p, c->gath64.p, sizeof(mine) * W, hipMemcpyDeviceToHost,
                         c->stream));
   sync(c);
-  static const char* what[K] = {"round", "inliers", "coefficients", "coefficients", "collectives"};
+  static const char* what[K] = {"round", "inliers", "coefficients", "coefficients", "collectives",
+                                "axis", "axis", "eps_angle"};
   for (int r = 1; r < W; ++r)
     for (int k = 0; k < K; ++k)
       if (c->h_g64.p[(size_t)K * r + k] != c->h_g64.p[k])

@@ -25,6 +25,9 @@ struct SegOut {
 SegOut segment_round(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params& prm, bool compact,
                      dlg_sac_stats* st, dlg_extract_stats* xs,
                      const std::vector<int64_t>* active_ranks = nullptr);
+void score_samples(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params& prm, const int32_t* positions,
+                   int D, int32_t* counts_out, int32_t* good_out, int32_t* valid_out,
+                   float* coeffs_out);
 void commit_round(dlg_cloud* cl, const SegOut& so);
 void check_in_step(dlg_ctx* c, int round, const SegOut& so);
 int64_t emit_inliers(dlg_ctx* c, const SegOut& so, bool gather, int32_t* dst, int64_t cap,

@@ -22,6 +22,8 @@ from ._lib import DLG_REFIT_FAST, DLG_REFIT_PCL, DLG_SACMODEL_PLANE, DialogError
 
 SACMODEL_PLANE = 0
 SACMODEL_NORMAL_PLANE = 11
+SACMODEL_PERPENDICULAR_PLANE = 9
+SACMODEL_PARALLEL_PLANE = 15
 SAC_RANSAC = 0
 
 
@@ -121,6 +123,19 @@ class Context:
         v = C.c_int64()
         self.check(self._L.dlg_ctx_get_option(self.h, int(option), C.byref(v)))
         return v.value
+
+    def set_axis(self, axis, eps_angle: float):
+        """dlg_ctx_set_axis: SACSegmentation::setAxis / setEpsAngle (radians) for the models
+        SACMODEL_PERPENDICULAR_PLANE and SACMODEL_PARALLEL_PLANE; context state."""
+        a = np.ascontiguousarray(axis, np.float32).reshape(3)
+        self.check(self._L.dlg_ctx_set_axis(self.h, _f32p(a), float(eps_angle)))
+
+    def get_axis(self):
+        """-> (axis float32[3], eps_angle)"""
+        a = np.zeros(3, np.float32)
+        e = C.c_double()
+        self.check(self._L.dlg_ctx_get_axis(self.h, _f32p(a), C.byref(e)))
+        return a, e.value
 
     def prune_stats(self, reset: bool = False) -> dict:
         """The pruned scoring kernel's work counters (needs DLG_OPT_PRUNE_STATS = 1)."""
@@ -312,6 +327,36 @@ def segment_cloud(cloud: Cloud, params, capacity=None):
     return inl[:n.value], coeff, _stats_dict(st)  # a view: the buffer is this call's own
 
 
+def score_samples(cloud: Cloud, params, positions):
+    """dlg_score_samples: the round's gather, hypothesis build and scoring over the caller's
+    draws (int32 [D, 3] positions into the global active list, as RansacControl.next() returns
+    them; 1 <= D <= 4096) for params.model on the path a segment() of this cloud takes
+    -> dict(counts int32[D], good int32[D], valid int32[D], coeffs float32[D, 4])."""
+    ctx = cloud.ctx
+    pos = np.ascontiguousarray(positions, np.int32).reshape(-1, 3)
+    d = pos.shape[0]
+    counts = np.zeros(max(d, 1), np.int32)
+    good = np.zeros(max(d, 1), np.int32)
+    valid = np.zeros(max(d, 1), np.int32)
+    coeffs = np.zeros((max(d, 1), 4), np.float32)
+    ctx.check(ctx._L.dlg_score_samples(ctx.h, cloud.h, C.byref(params), _i32p(pos), d,
+                                       _i32p(counts), _i32p(good), _i32p(valid), _f32p(coeffs)))
+    return dict(counts=counts[:d], good=good[:d], valid=valid[:d], coeffs=coeffs[:d])
+
+
+def axis_verdicts(model: int, eps_angle: float, f):
+    """dlg_axis_verdicts (host arithmetic, tests): the constrained models' verdicts on the float
+    dot products f -> (by_threshold int32[], by_formula int32[], (t_lo, t_hi))."""
+    L = _lib.load()
+    a = np.ascontiguousarray(f, np.float32).reshape(-1)
+    bt = np.zeros(max(a.size, 1), np.int32)
+    bf = np.zeros(max(a.size, 1), np.int32)
+    thr = np.zeros(2, np.float32)
+    _lib.check(L.dlg_axis_verdicts(int(model), float(eps_angle), _f32p(a), a.size, _i32p(bt),
+                                   _i32p(bf), _f32p(thr)))
+    return bt[:a.size], bf[:a.size], (thr[0], thr[1])
+
+
 def extract_planes(cloud: Cloud, params, max_planes=20, min_inliers=0, capacity=None, out=None):
     """Sequential extract-and-remove -> dict(coeffs [P,4], offsets [P+1], inliers, stats).
 
@@ -414,7 +459,8 @@ def default_context() -> Context:
 
 
 class SACSegmentation:
-    """pcl::SACSegmentation<pcl::PointXYZ> (SACMODEL_PLANE, SAC_RANSAC) on the GPU."""
+    """pcl::SACSegmentation<pcl::PointXYZ> (SACMODEL_PLANE and the axis-constrained
+    SACMODEL_PERPENDICULAR_PLANE / SACMODEL_PARALLEL_PLANE, SAC_RANSAC) on the GPU."""
 
     def __init__(self, ctx: Context | None = None):
         self.ctx = ctx
@@ -428,8 +474,10 @@ class SACSegmentation:
         self.input = None
         self.indices = None
         self.last_stats = None
+        self.axis = np.zeros(3, np.float32)
+        self.eps_angle = 0.0
 
-    _models = (SACMODEL_PLANE,)
+    _models = (SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE, SACMODEL_PARALLEL_PLANE)
 
     def _attach(self, cloud):
         pass
@@ -462,6 +510,20 @@ class SACSegmentation:
     def setRefitMode(self, mode):
         self.refit_mode = int(mode)
 
+    def setAxis(self, axis):
+        """SACSegmentation::setAxis: read by SACMODEL_PERPENDICULAR_PLANE / SACMODEL_PARALLEL_PLANE"""
+        self.axis = np.ascontiguousarray(axis, np.float32).reshape(3).copy()
+
+    def getAxis(self):
+        return self.axis.copy()
+
+    def setEpsAngle(self, ea):
+        """SACSegmentation::setEpsAngle (radians)"""
+        self.eps_angle = float(ea)
+
+    def getEpsAngle(self):
+        return self.eps_angle
+
     def segment(self):
         """-> (inliers int32[], coefficients float32[4] or [] when no model was found)."""
         if self.input is None:
@@ -475,6 +537,8 @@ class SACSegmentation:
         params = make_params(self.threshold, self.max_iterations, self.probability, self.optimize,
                              refit_mode=self.refit_mode, model=self.model_type,
                              normal_distance_weight=getattr(self, "normal_distance_weight", 0.1))
+        if self.model_type in (SACMODEL_PERPENDICULAR_PLANE, SACMODEL_PARALLEL_PLANE):
+            ctx.set_axis(self.axis, self.eps_angle)
         cloud = Cloud(ctx, self.input, indices=self.indices)
         try:
             self._attach(cloud)
@@ -495,12 +559,14 @@ class SACSegmentation:
     set_optimize_coefficients = setOptimizeCoefficients
     set_input_cloud = setInputCloud
     set_indices = setIndices
+    set_axis = setAxis
+    set_eps_angle = setEpsAngle
 
 
 class SACSegmentationFromNormals(SACSegmentation):
     """pcl::SACSegmentationFromNormals<PointXYZ, Normal> (SACMODEL_NORMAL_PLANE, SAC_RANSAC)."""
 
-    _models = (SACMODEL_PLANE, SACMODEL_NORMAL_PLANE)
+    _models = SACSegmentation._models + (SACMODEL_NORMAL_PLANE,)
 
     def __init__(self, ctx: Context | None = None):
         super().__init__(ctx)

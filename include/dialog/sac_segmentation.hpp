@@ -8,6 +8,8 @@
 //   * the plane-stage slot of Dialog/PlaneDetect.h:667-1355 that fills
 //     `plane_clouds` (PlaneDetect.h:100, struct Plane HeaderFile.h:81-88) ->
 //     dialog::extractPlanes(cloud, params, planes) (sequential extract-and-remove RANSAC);
+//     with SACMODEL_PLANE, or with setAxis / setEpsAngle and SACMODEL_PERPENDICULAR_PLANE /
+//     SACMODEL_PARALLEL_PLANE;
 //   * pcl::SACSegmentationFromNormals (SACMODEL_NORMAL_PLANE) -> dialog::SACSegmentationFromNormals;
 //   * estimateNormal() (PlaneDetect.h:515-545, pcl::NormalEstimationOMP with a radius; k = 20 at
 //     PCLViewer.cpp:507-522) -> dialog::NormalEstimation<PointT, pcl::Normal>;
@@ -23,6 +25,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <memory>
@@ -69,12 +72,20 @@ struct PointIndices {
   typedef std::shared_ptr<PointIndices> Ptr;
   std::vector<int> indices;
 };
-enum SacModel { SACMODEL_PLANE = 0, SACMODEL_NORMAL_PLANE = 11 };
+enum SacModel {
+  SACMODEL_PLANE = 0,
+  SACMODEL_PERPENDICULAR_PLANE = 9,
+  SACMODEL_NORMAL_PLANE = 11,
+  SACMODEL_PARALLEL_PLANE = 15
+};
 static const int SAC_RANSAC = 0;
 }  // namespace pcl
 #endif
 
 static_assert(sizeof(pcl::PointXYZ) == 16, "pcl::PointXYZ must be 16 bytes (x, y, z, pad)");
+static_assert((int)pcl::SACMODEL_PERPENDICULAR_PLANE == DLG_SACMODEL_PERPENDICULAR_PLANE &&
+                  (int)pcl::SACMODEL_PARALLEL_PLANE == DLG_SACMODEL_PARALLEL_PLANE,
+              "pcl::SacModel values are passed to the C ABI as they are");
 
 namespace dialog {
 
@@ -121,6 +132,13 @@ class SACSegmentation {
   void setMaxIterations(int n) { prm_.max_iterations = n; }
   void setProbability(double p) { prm_.probability = p; }
   void setOptimizeCoefficients(bool b) { prm_.optimize = b ? 1 : 0; }
+  // SACMODEL_PERPENDICULAR_PLANE / SACMODEL_PARALLEL_PLANE: the axis (any type with ax[0..2]:
+  // float[3], Eigen::Vector3f; not normalised) and the angle in radians (dlg_ctx_set_axis)
+  template <typename Vec3>
+  void setAxis(const Vec3& ax) { axis_ = {(float)ax[0], (float)ax[1], (float)ax[2]}; }
+  std::array<float, 3> getAxis() const { return axis_; }
+  void setEpsAngle(double ea) { eps_angle_ = ea; }
+  double getEpsAngle() const { return eps_angle_; }
   // extension: DLG_REFIT_PCL (bit-exact with PCL, default) or DLG_REFIT_FAST
   void setRefitMode(int m) { prm_.refit_mode = m; }
   const dlg_sac_stats& lastStats() const { return stats_; }
@@ -132,12 +150,15 @@ class SACSegmentation {
       std::fprintf(stderr, "[dialog::SACSegmentation::segment] No input dataset given!\n");
       return;
     }
-    if (model_ != pcl::SACMODEL_PLANE || method_ != pcl::SAC_RANSAC) {
+    const bool constrained =
+        model_ == pcl::SACMODEL_PERPENDICULAR_PLANE || model_ == pcl::SACMODEL_PARALLEL_PLANE;
+    if ((model_ != pcl::SACMODEL_PLANE && !constrained) || method_ != pcl::SAC_RANSAC) {
       std::fprintf(stderr, "[dialog::SACSegmentation::segment] Error initializing the SAC model!\n");
       return;
     }
-    prm_.model = DLG_SACMODEL_PLANE;
+    prm_.model = model_;  // (pcl::SacModel's values are the C ABI's)
     dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    if (constrained) check(dlg_ctx_set_axis(c, axis_.data(), eps_angle_), c);
     dlg_points pts{input_->points.empty() ? nullptr : &input_->points[0].x,
                    (int64_t)input_->points.size(), (int64_t)sizeof(PointT)};
     const int64_t n = has_idx_ ? (int64_t)indices_.size() : pts.n;
@@ -164,6 +185,8 @@ class SACSegmentation {
   std::vector<int> indices_;
   bool has_idx_ = false;
   int model_ = -1, method_ = -1;
+  std::array<float, 3> axis_{{0.f, 0.f, 0.f}};
+  double eps_angle_ = 0.0;
 };
 
 // pcl::SACSegmentationFromNormals<PointT, pcl::Normal>: SACMODEL_NORMAL_PLANE (or PLANE) with the
@@ -410,6 +433,12 @@ struct ExtractParams {
   // SACMODEL_NORMAL_PLANE when set: one pcl::Normal per cloud point
   const pcl::PointCloud<pcl::Normal>* normals = nullptr;
   double normal_distance_weight = 0.1;
+  // axis-constrained extraction (without normals): pcl::SACMODEL_PERPENDICULAR_PLANE ("the
+  // horizontal planes": normal within eps_angle of axis) or pcl::SACMODEL_PARALLEL_PLANE ("the
+  // vertical planes only"); pcl::SACMODEL_PLANE (default) ignores axis and eps_angle
+  int model = pcl::SACMODEL_PLANE;
+  float axis[3] = {0.f, 0.f, 0.f};
+  double eps_angle = 0.0;  // radians
 };
 
 template <typename PointT>
@@ -430,6 +459,9 @@ inline dlg_extract_stats extractPlanes(const pcl::PointCloud<PointT>& cloud, con
           c);
     prm.model = DLG_SACMODEL_NORMAL_PLANE;
     prm.normal_distance_weight = ep.normal_distance_weight;
+  } else if (ep.model == pcl::SACMODEL_PERPENDICULAR_PLANE || ep.model == pcl::SACMODEL_PARALLEL_PLANE) {
+    check(dlg_ctx_set_axis(c, ep.axis, ep.eps_angle), c);
+    prm.model = ep.model;
   }
   prm.threshold = ep.threshold;
   prm.max_iterations = ep.max_iterations;

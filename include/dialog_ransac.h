@@ -45,7 +45,9 @@ extern "C" {
  * DLG_OPT_SYNC_CHECK, DLG_OPT_COMM_TIMEOUT_MS, DLG_OPT_SEL1_TICKET, DLG_OPT_BOUNDS_STREAM;
  * DLG_OPT_SPATIAL_CURVE, DLG_OPT_FS_JOIN, DLG_OPT_UNREFINED_LIST (same ABI version: added options);
  * DLG_OPT_HYP_SHARD defaults to -1 (automatic); dlg_shard_range; dlg_cloud_signature (same ABI
- * version: an added entry) */
+ * version: an added entry); DLG_SACMODEL_PERPENDICULAR_PLANE, DLG_SACMODEL_PARALLEL_PLANE,
+ * dlg_ctx_set_axis / dlg_ctx_get_axis, dlg_score_samples, dlg_axis_verdicts (same ABI version: an
+ * added enum value and added entries) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -62,7 +64,15 @@ typedef enum {
 } dlg_status;
 
 /* pcl::SacModel values (pcl/sample_consensus/model_types.h) */
-enum { DLG_SACMODEL_PLANE = 0, DLG_SACMODEL_NORMAL_PLANE = 11 };
+enum {
+  DLG_SACMODEL_PLANE = 0,
+  DLG_SACMODEL_NORMAL_PLANE = 11,
+  /* SACMODEL_PLANE with isModelValid against the context's axis (dlg_ctx_set_axis): a
+     hypothesis that fails it counts 0 inliers inside the RANSAC loop and selects none */
+  DLG_SACMODEL_PERPENDICULAR_PLANE = 9, /* the plane's normal within eps_angle of the axis */
+  DLG_SACMODEL_PARALLEL_PLANE = 15      /* the plane's normal perpendicular to the axis within
+                                           eps_angle (the plane is parallel to the axis) */
+};
 /* refit of the winning model (SampleConsensusModelPlane::optimizeModelCoefficients) */
 enum {
   DLG_REFIT_PCL = 0,   /* PCL's float refit: computeMeanAndCovarianceMatrix's single-pass float
@@ -91,7 +101,9 @@ typedef struct {
   double probability;          /* setProbability (PCL default 0.99) */
   int optimize;                /* setOptimizeCoefficients (PCL default 1) */
   uint32_t seed;               /* 12345u = PCL's non-random seed */
-  int model;                   /* DLG_SACMODEL_PLANE | DLG_SACMODEL_NORMAL_PLANE (needs normals) */
+  int model;                   /* DLG_SACMODEL_PLANE | DLG_SACMODEL_NORMAL_PLANE (needs normals) |
+                                  DLG_SACMODEL_PERPENDICULAR_PLANE | DLG_SACMODEL_PARALLEL_PLANE
+                                  (axis and eps_angle: dlg_ctx_set_axis) */
   double normal_distance_weight; /* SACSegmentationFromNormals::setNormalDistanceWeight (0.1) */
   int refit_mode;              /* DLG_REFIT_PCL (default) | DLG_REFIT_FAST */
   int hypotheses_per_launch;   /* upper bound of one scoring launch; 0 = 4096 */
@@ -160,6 +172,24 @@ dlg_status dlg_ctx_create_dist(dlg_ctx** out, int device, int rank, int world,
 dlg_status dlg_ctx_create_loopback_group(dlg_ctx** out_array, int world, int device);
 dlg_status dlg_ctx_destroy(dlg_ctx* ctx);
 const char* dlg_last_error(const dlg_ctx* ctx);
+/* SACSegmentation::setAxis / setEpsAngle: the axis (not normalised by the caller or on storing) and
+ * the angle in radians that DLG_SACMODEL_PERPENDICULAR_PLANE and DLG_SACMODEL_PARALLEL_PLANE test
+ * a hypothesis against; context state, (0, 0, 0) and 0 by default, read by every call whose
+ * prm->model is one of the two.  eps_angle <= 0 accepts every plane (both models are then
+ * SACMODEL_PLANE bit for bit).  A NaN or infinite axis component or a NaN eps_angle:
+ * DLG_ERR_INVALID.  Several ranks: every rank must set the same values (DLG_OPT_SYNC_CHECK
+ * compares them).  The arithmetic is PCL 1.8's isModelValid restated from memory (parity
+ * unpinned):
+ *   Cn = (c0, c1, c2, 0).normalized() of the plane's float coefficients
+ *   perpendicular: rad = clamp(axis.normalized() . Cn, -1, 1) (float dot, double clamp),
+ *                  invalid when min(acos(rad), M_PI - acos(rad)) > eps_angle
+ *   parallel     : invalid when |axis . Cn| (float, the axis as given) > |sin(eps_angle)|
+ * An invalid hypothesis from a good sample is an ordinary iteration with 0 inliers (it is not a
+ * skipped sample), so when every hypothesis is invalid the first good draw wins: has_model = 1,
+ * its real coefficients reported, 0 inliers.  The refit is SACMODEL_PLANE's (unconstrained); a
+ * refined plane that fails the test is reported with 0 inliers. */
+dlg_status dlg_ctx_set_axis(dlg_ctx* ctx, const float axis[3], double eps_angle);
+dlg_status dlg_ctx_get_axis(const dlg_ctx* ctx, float axis[3], double* eps_angle);
 dlg_status dlg_ctx_info(const dlg_ctx* ctx, int* rank, int* world, int* device);
 
 /* ---- device-resident clouds (this rank's contiguous shard of the global index order) -------- */
@@ -407,6 +437,36 @@ dlg_status dlg_sac_control_consume(dlg_sac_control* ctl, const int32_t* counts,
 dlg_status dlg_sac_control_result(const dlg_sac_control* ctl, dlg_sac_stats* st,
                                   int64_t* best_draw);
 
+/* The device half of the pair above: countWithinDistance of the caller's draws.  positions:
+ * 3 * n_draws positions into the global active list, exactly what dlg_sac_control_next hands out
+ * (1 <= n_draws <= 4096; a position outside the list: DLG_ERR_INVALID).  Runs the gather, the
+ * hypothesis build and the scoring of a dlg_sac_segment round for prm->model (any of the four)
+ * on the path that round would take for this cloud -- the exhaustive, pruned or pruned
+ * NORMAL_PLANE scorer, at several ranks the sample and count allreduces or the hypothesis
+ * slices -- and leaves the active list as it is.  Per draw, in draw order:
+ *   counts_out  inliers of the draw's plane among the active points (all ranks); 0 for a bad
+ *               sample and for a plane the axis-constrained models reject
+ *   good_out    isSampleGood
+ *   valid_out   (nullable) isModelValid: 0 only for a good sample whose plane
+ *               DLG_SACMODEL_PERPENDICULAR_PLANE / DLG_SACMODEL_PARALLEL_PLANE reject
+ *   coeffs_out  (nullable) 4 floats: computeModelCoefficients, also of a rejected plane; NaN for
+ *               a bad sample
+ * counts_out and good_out are what dlg_sac_control_consume takes.  Several ranks: every rank
+ * calls it with the same positions. */
+dlg_status dlg_score_samples(dlg_ctx* ctx, dlg_cloud* cloud, const dlg_sac_params* prm,
+                             const int32_t* positions, int n_draws, int32_t* counts_out,
+                             int32_t* good_out, int32_t* valid_out, float* coeffs_out);
+/* Tests: the verdicts of the axis-constrained models on n values f of the float dot product
+ * their test reduces to (perpendicular: axis.normalized() . Cn, parallel: axis . Cn).
+ * by_threshold[i]: from the float thresholds the host derives from eps_angle once per call and
+ * the device compares against (perpendicular: valid when f >= thresholds[1] or f <=
+ * thresholds[0], found by bisection over float bit patterns; parallel: invalid when |f| >
+ * thresholds[1], the largest float <= |sin(eps_angle)|); by_formula[i]: from the acos / sin
+ * formula of dlg_ctx_set_axis evaluated directly in double.  The two must agree for every f.
+ * model: one of the two constrained models.  Host arithmetic; no context. */
+dlg_status dlg_axis_verdicts(int model, double eps_angle, const float* f, int64_t n,
+                             int32_t* by_threshold, int32_t* by_formula, float thresholds[2]);
+
 /* ---- profiling ------------------------------------------------------------------------------ */
 /* Kernel-level HIP-event timing on the context's stream (bench roofline); off by default.
  * enable 1: the scoring launches, the select phase and the PCL refit walk; 2: without the walk's
@@ -516,8 +576,9 @@ enum {
                                (default).  Exercises the group abort: every peer returns
                                DLG_ERR_COMM naming the failed rank */
   DLG_OPT_SYNC_CHECK = 17,  /* several ranks, debug: 1 = after every extract round the ranks
-                               allgather (round, inliers, coefficient bits, collectives issued)
-                               and fail the call (aborting the group) on any mismatch; 0 (default) */
+                               allgather (round, inliers, coefficient bits, collectives issued,
+                               the axis bits and eps_angle of dlg_ctx_set_axis) and fail the call
+                               (aborting the group) on any mismatch; 0 (default) */
   DLG_OPT_COMM_TIMEOUT_MS = 18, /* several ranks: a host wait on the group (a stream holding an
                                RCCL collective, a round's results) that makes no progress for this
                                long aborts the group (DLG_ERR_COMM on every rank); 0 = no limit;
