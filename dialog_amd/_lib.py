@@ -38,6 +38,7 @@ SYMBOLS = [
     "dlg_abi_struct_size", "dlg_float_sums", "dlg_cloud_estimate_normals", "dlg_plane_border",
     "dlg_cloud_regulate_normals", "dlg_shard_range", "dlg_cloud_signature",
     "dlg_ctx_set_axis", "dlg_ctx_get_axis", "dlg_score_samples", "dlg_axis_verdicts",
+    "dlg_voxel_grid", "dlg_voxel_grid_cloud",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -64,6 +65,7 @@ DLG_OPT_BOUNDS_STREAM = 20
 DLG_OPT_SPATIAL_CURVE = 21
 DLG_OPT_FS_JOIN = 22
 DLG_OPT_UNREFINED_LIST = 23
+DLG_OPT_VOXEL_LONG_RUN = 24
 DLG_TILE_EXACT = 0
 DLG_TILE_BF16 = 1
 DLG_TILE_MFMA = 2
@@ -87,6 +89,15 @@ class PostProcessParams(C.Structure):
     _fields_ = [("t_dist_point_plane", C.c_float), ("radius_local", C.c_float),
                 ("t_cluster_num", C.c_int32), ("plane_start_index", C.c_int32),
                 ("rand_seed", C.c_uint32)]
+
+
+class VoxelParams(C.Structure):
+    _fields_ = [("leaf", C.c_float * 3), ("min_points_per_voxel", C.c_int32)]
+
+
+class VoxelStats(C.Structure):
+    _fields_ = [("n_finite", C.c_int64), ("n_voxels", C.c_int64), ("div", C.c_int32 * 3),
+                ("min_b", C.c_int32 * 3), ("device_ms", C.c_double)]
 
 
 class SacParams(C.Structure):
@@ -208,6 +219,12 @@ def load():
     L.dlg_axis_verdicts.argtypes = [C.c_int, C.c_double, fp, C.c_int64, i32p, i32p, fp]
     L.dlg_cluster_filter.argtypes = [vp, C.POINTER(Points), C.c_float, C.c_int32, i32p,
                                      C.c_int64, i64p]
+    L.dlg_voxel_grid.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64, C.POINTER(VoxelParams),
+                                 fp, C.c_int64, C.c_int64, i64p, i32p, i32p,
+                                 C.POINTER(VoxelStats)]
+    L.dlg_voxel_grid_cloud.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
+                                       C.POINTER(VoxelParams), C.c_int32, pp, i64p, i32p,
+                                       C.POINTER(VoxelStats)]
     for s in SYMBOLS:
         if s not in ("dlg_abi_version", "dlg_status_string", "dlg_sac_params_default",
                      "dlg_last_error", "dlg_abi_struct_size"):

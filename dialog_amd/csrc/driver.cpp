@@ -123,6 +123,25 @@ void dlg::attach_normals(dlg_ctx* c, dlg_cloud* cl, const float* raw_dev, int64_
   }
 }
 
+void dlg::finish_upload(dlg_ctx* c, dlg_cloud* cl, int64_t n) {
+  c->totals.ensure(8);
+  launch_absmax(cl->pristine.view(n), reinterpret_cast<uint32_t*>(c->totals.p), c->stream);
+  uint32_t bits[4];
+  HIPCHK(hipMemcpyAsync(bits, c->totals.p, 16, hipMemcpyDeviceToHost, c->stream));
+  sync(c);
+  for (int k = 0; k < 3; ++k) std::memcpy(&cl->amax[k], &bits[k], 4);
+  std::memcpy(&cl->fmax, &bits[3], 4);
+  if (c->opt.prune != 0 && n >= 3 && (n >= kPruneMinPoints || c->opt.prune == 1))
+    build_spatial(c, cl);
+}
+
+void dlg::release_cloud_buffers(dlg_cloud* cl) {
+  cl->pristine.release();
+  cl->sp_pristine.release();
+  cl->sp_tiles_pr.release();
+  cl->sp_supers_pr.release();
+}
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -138,6 +157,8 @@ int64_t dlg_abi_struct_size(int which) {
     case 3: return (int64_t)sizeof(dlg_extract_stats);
     case 4: return (int64_t)sizeof(dlg_planes);
     case 5: return (int64_t)sizeof(dlg_postprocess_params);
+    case 6: return (int64_t)sizeof(dlg_voxel_params);
+    case 7: return (int64_t)sizeof(dlg_voxel_stats);
   }
   return -1;
 }
@@ -257,6 +278,7 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   c->pub_cap = 0;
   c->nw.release();
   c->pw.release();
+  c->vw.release();
   c->pstats.release();
   c->sel1_status.release();
   c->sel1_err.release();
@@ -356,21 +378,10 @@ dlg_status dlg_cloud_upload(dlg_ctx* c, const dlg_points* pts, const int32_t* in
       HIPCHK(hipMemcpyAsync(cl->pristine.gid.p, g.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
       sync(c);  // the host vectors go out of scope
     }
-    c->totals.ensure(8);
-    launch_absmax(cl->pristine.view(n), reinterpret_cast<uint32_t*>(c->totals.p), c->stream);
-    uint32_t bits[4];
-    HIPCHK(hipMemcpyAsync(bits, c->totals.p, 16, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    for (int k = 0; k < 3; ++k) std::memcpy(&cl->amax[k], &bits[k], 4);
-    std::memcpy(&cl->fmax, &bits[3], 4);
-    if (c->opt.prune != 0 && n >= 3 && (n >= kPruneMinPoints || c->opt.prune == 1))
-      build_spatial(c, cl.get());
+    finish_upload(c, cl.get(), n);
   });
   if (s != DLG_OK) {
-    cl->pristine.release();
-    cl->sp_pristine.release();
-    cl->sp_tiles_pr.release();
-    cl->sp_supers_pr.release();
+    release_cloud_buffers(cl.get());
     return s;
   }
   *out = cl.release();
@@ -827,6 +838,7 @@ const OptRow kOptions[] = {
     OPT(DLG_OPT_SPATIAL_CURVE, spatial_curve, 0, 1, "0 or 1"),
     OPT_BOOL(DLG_OPT_FS_JOIN, fs_join),
     OPT_BOOL(DLG_OPT_UNREFINED_LIST, unrefined_list),
+    OPT(DLG_OPT_VOXEL_LONG_RUN, voxel_long_run, 1, INT32_MAX, "1..2147483647"),
 };
 #undef OPT_BOOL
 #undef OPT

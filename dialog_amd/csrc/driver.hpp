@@ -153,6 +153,21 @@ struct PostWork {
   }
 };
 
+// scratch of the voxel-grid filter (voxel_host.cpp; the list-order coordinates and records, the raw
+// upload and the hipcub temporaries are the normals path's nw.x/y/z, nw.rec, nw.raw, nw.sort_tmp)
+struct VoxelWork {
+  DevBuf<uint8_t> flags, lflag;
+  DevBuf<uint32_t> keys_in, keys_out;
+  DevBuf<int32_t> fin_pos, pos_in, pos_out, head, vid, vstart, keep, row, long_list, ocnt, voe;
+  DevBuf<float> sx, sy, sz, ox, oy, oz;
+  void release() {
+    flags.release(); lflag.release(); keys_in.release(); keys_out.release(); fin_pos.release();
+    pos_in.release(); pos_out.release(); head.release(); vid.release(); vstart.release();
+    keep.release(); row.release(); long_list.release(); ocnt.release(); voe.release();
+    sx.release(); sy.release(); sz.release(); ox.release(); oy.release(); oz.release();
+  }
+};
+
 }  // namespace dlg
 
 using namespace dlg;
@@ -195,6 +210,8 @@ struct PathOptions {
   int spatial_curve = 1;  // DLG_OPT_SPATIAL_CURVE: 1 Hilbert, 0 Morton order of the spatial copy
   int fs_join = 1;     // DLG_OPT_FS_JOIN: segmented walk's joins by each chain's last walker
   int unrefined_list = 1;   // DLG_OPT_UNREFINED_LIST: lean PCL refit's inliers by one list pass
+  int voxel_long_run = 32;  // DLG_OPT_VOXEL_LONG_RUN: voxels of this many points or more are summed
+                            // by one wave each (voxel.hip), smaller ones by one thread each
 };
 
 struct dlg_ctx {
@@ -296,6 +313,7 @@ struct dlg_ctx {
   int64_t emit_n = 0;
   NormalsWork nw;
   PostWork pw;
+  VoxelWork vw;
   // PCL float refit on the device (fsum.hip): scratch sized for fs_cap inliers
   DevBuf<uint8_t> fs_scr;
   // the spatial index build's sort scratch (Morton keys and orders, ping-pong; radix-sort
@@ -409,6 +427,12 @@ dlg_status guarded_group(dlg_ctx* c, F&& f) {
     c->group()->abort("rank " + std::to_string(c->group()->rank()) + " failed: " + c->err);
   return s;
 }
+
+// the tail of an upload, shared by dlg_cloud_upload and dlg_voxel_grid_cloud: the cloud's n points
+// and ids are in its pristine list on the device; computes amax / fmax and builds the spatial copy
+// under DLG_OPT_PRUNE's rule.  release_cloud_buffers: what a failed upload frees before the delete.
+void finish_upload(dlg_ctx* c, dlg_cloud* cl, int64_t n);
+void release_cloud_buffers(dlg_cloud* cl);
 
 // normals on the device -> the cloud (dlg_cloud_set_normals, dlg_cloud_estimate_normals)
 void attach_normals(dlg_ctx* c, dlg_cloud* cl, const float* raw_dev, int64_t stride_f,

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .sac import Context, _f32p, _i32p, _points, default_context
+from .sac import Cloud, Context, _f32p, _i32p, _points, default_context
 
 
 def preprocess(points, min_dist: float, translate: bool = True, ctx: Context | None = None):
@@ -25,6 +25,62 @@ def preprocess(points, min_dist: float, translate: bool = True, ctx: Context | N
                                          float(min_dist), _f32p(out), 12, _i32p(idx), n,
                                          C.byref(k), _f32p(tr)))
     return out[:k.value].copy(), idx[:k.value].copy(), tr
+
+
+def _voxel_args(points, leaf, indices, min_points):
+    a, pts = _points(points)
+    lf = np.broadcast_to(np.asarray(leaf, np.float32), (3,))
+    prm = _lib.VoxelParams((C.c_float * 3)(*[float(v) for v in lf]), int(min_points))
+    idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.int32)
+    n = a.shape[0] if idx is None else idx.shape[0]
+    return a, pts, prm, idx, n
+
+
+def _voxel_stats(st):
+    return dict(n_finite=st.n_finite, n_voxels=st.n_voxels, div=np.array(st.div[:], np.int32),
+                min_b=np.array(st.min_b[:], np.int32), device_ms=st.device_ms)
+
+
+def voxel_grid(points, leaf, indices=None, min_points: int = 0, ctx: Context | None = None,
+               return_stats: bool = False):
+    """pcl::VoxelGrid<PointXYZ>::filter on the GPU (dlg_voxel_grid; PCLViewer.cpp:313-332): one
+    centroid per occupied voxel of edge lengths `leaf` (a scalar or 3 values), in key order.
+    indices: setIndices (any order, duplicates allowed); min_points:
+    setMinimumPointsNumberPerVoxel.  -> (xyz float32 [k,3], counts int32 [k], voxel_of_entry
+    int32 [n]: the output row of each list entry, -1 for a non-finite entry or a dropped voxel)
+    [, stats dict].  A leaf too small for 32-bit voxel indices raises DialogError (status 1)."""
+    ctx = ctx or default_context()
+    a, pts, prm, idx, n = _voxel_args(points, leaf, indices, min_points)
+    out = np.empty((max(n, 1), 3), np.float32)
+    cnt = np.empty(max(n, 1), np.int32)
+    voe = np.empty(max(n, 1), np.int32)
+    k = C.c_int64(0)
+    st = _lib.VoxelStats()
+    ctx.check(_lib.load().dlg_voxel_grid(ctx.h, C.byref(pts), None if idx is None else _i32p(idx),
+                                         n if idx is not None else 0, C.byref(prm), _f32p(out), 12,
+                                         n, C.byref(k), _i32p(cnt), _i32p(voe), C.byref(st)))
+    res = (out[:k.value].copy(), cnt[:k.value].copy(), voe[:n].copy())
+    return res + (_voxel_stats(st),) if return_stats else res
+
+
+def voxel_grid_cloud(points, leaf, indices=None, min_points: int = 0, id_base: int = 0,
+                     ctx: Context | None = None, return_stats: bool = False):
+    """voxel_grid with the result left on the device (dlg_voxel_grid_cloud): -> (Cloud,
+    voxel_of_entry int32 [n]) [, stats dict].  The Cloud equals Cloud(ctx, xyz, id_base=id_base) of
+    the points voxel_grid returns, so normals and planes run on it with no host round trip."""
+    ctx = ctx or default_context()
+    a, pts, prm, idx, n = _voxel_args(points, leaf, indices, min_points)
+    voe = np.empty(max(n, 1), np.int32)
+    k = C.c_int64(0)
+    h = C.c_void_p()
+    st = _lib.VoxelStats()
+    ctx.check(_lib.load().dlg_voxel_grid_cloud(ctx.h, C.byref(pts),
+                                               None if idx is None else _i32p(idx),
+                                               n if idx is not None else 0, C.byref(prm),
+                                               int(id_base), C.byref(h), C.byref(k), _i32p(voe),
+                                               C.byref(st)))
+    res = (Cloud._from_handle(ctx, h, k.value), voe[:n].copy())
+    return res + (_voxel_stats(st),) if return_stats else res
 
 
 def remove_redundant_points(points, min_dist: float, ctx: Context | None = None):

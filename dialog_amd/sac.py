@@ -198,6 +198,16 @@ class Cloud:
         self.h = h
         _LIVE_CLOUDS.add(self)
 
+    @classmethod
+    def _from_handle(cls, ctx: Context, handle, n: int):
+        """A cloud the library built on the device itself (voxel_grid_cloud): n points."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.n = int(n)
+        self.h = handle
+        _LIVE_CLOUDS.add(self)
+        return self
+
     def build_spatial(self):
         """Morton-ordered copy for the pruned scoring kernel (automatic for >= 131072 points)."""
         self.ctx.check(self.ctx._L.dlg_cloud_build_spatial(self.ctx.h, self.h))

@@ -15,7 +15,8 @@
 //     PCLViewer.cpp:507-522) -> dialog::NormalEstimation<PointT, pcl::Normal>;
 //   * regulateNormal() (PlaneDetect.h:547-665) -> dialog::regulateNormals (first round) and
 //     dialog::orientNormalsToBackup (later rounds);
-//   * preProcess() (PlaneDetect.h:448-512) -> dialog::preProcess.
+//   * preProcess() (PlaneDetect.h:448-512) -> dialog::preProcess;
+//   * pcl::VoxelGrid<PointT> (PCLViewer.cpp:245-253, 283-300, 313-332) -> dialog::VoxelGrid<PointT>.
 // With real PCL available define DIALOG_HAVE_PCL before including; otherwise minimal
 // layout-identical stand-ins for pcl::PointXYZ (16 B), pcl::Normal (32 B), pcl::PointCloud,
 // pcl::ModelCoefficients and pcl::PointIndices are declared here.
@@ -346,6 +347,80 @@ inline void preProcess(const pcl::PointCloud<PointT>& cloud, bool translate, flo
   if (kept_index) kept_index->assign(idx.begin(), idx.begin() + n);
   if (translation) { translation[0] = tr[0]; translation[1] = tr[1]; translation[2] = tr[2]; }
 }
+
+// pcl::VoxelGrid<PointT> as the reference calls it (PCLViewer.cpp:245-253, 283-300, 313-332):
+// setInputCloud / setIndices / setLeafSize / setMinimumPointsNumberPerVoxel / filter(output), on
+// dlg_voxel_grid.  filter() may write the cloud it reads (the reference passes *source_cloud for
+// both, :253).  A leaf too small for 32-bit voxel indices: PCL's warning on stderr and output =
+// input.  The order of a voxel's points in its sum is list order (PCL's std::sort leaves it
+// unspecified).  getVoxelOfPoint(): for every list entry of the last filter(), the
+// output point it went into (-1: non-finite, or its voxel had fewer than the minimum points) --
+// what maps a plane found on the filtered cloud back to the original points.
+template <typename PointT>
+class VoxelGrid {
+ public:
+  typedef typename pcl::PointCloud<PointT>::ConstPtr PointCloudConstPtr;
+  explicit VoxelGrid(Context* ctx = nullptr) : ctx_(ctx) {}
+  void setInputCloud(const PointCloudConstPtr& cloud) { input_ = cloud; }
+  void setIndices(const pcl::PointIndices::Ptr& idx) { indices_ = idx ? idx->indices : std::vector<int>(); has_idx_ = (bool)idx; }
+  void setIndices(const std::vector<int>& idx) { indices_ = idx; has_idx_ = true; }
+  void setLeafSize(float lx, float ly, float lz) { prm_.leaf[0] = lx; prm_.leaf[1] = ly; prm_.leaf[2] = lz; }
+  void setMinimumPointsNumberPerVoxel(unsigned int n) { prm_.min_points_per_voxel = (int32_t)n; }
+  unsigned int getMinimumPointsNumberPerVoxel() const { return (unsigned int)prm_.min_points_per_voxel; }
+  const std::vector<int>& getVoxelOfPoint() const { return voxel_of_; }
+  const dlg_voxel_stats& lastStats() const { return stats_; }
+
+  void filter(pcl::PointCloud<PointT>& output) {
+    static_assert(sizeof(PointT) == 16, "VoxelGrid writes pcl::PointXYZ records");
+    voxel_of_.clear();
+    if (!input_) {
+      std::fprintf(stderr, "[dialog::VoxelGrid::filter] No input dataset given!\n");
+      output.points.clear();
+      output.width = 0;
+      output.height = 1;
+      return;
+    }
+    dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    dlg_points pts{input_->points.empty() ? nullptr : &input_->points[0].x,
+                   (int64_t)input_->points.size(), (int64_t)sizeof(PointT)};
+    std::vector<int32_t> idx32(indices_.begin(), indices_.end());
+    const int64_t n = has_idx_ ? (int64_t)idx32.size() : pts.n;
+    if (n == 0) {  // (an empty index list has a null data(): the C ABI would read "no indices")
+      output.points.clear();
+      output.width = 0;
+      output.height = 1;
+      output.is_dense = true;
+      return;
+    }
+    std::vector<PointT> res((size_t)n);  // (a buffer of its own: output may be the input)
+    std::vector<int32_t> voe((size_t)(n > 0 ? n : 1));
+    int64_t k = 0;
+    const dlg_status s = dlg_voxel_grid(c, &pts, has_idx_ ? idx32.data() : nullptr, n, &prm_, &res[0].x,
+                                        (int64_t)sizeof(PointT), n, &k, nullptr, voe.data(), &stats_);
+    if (s == DLG_ERR_INVALID && std::string(dlg_last_error(c)).find("leaf size too small: voxel indices") == 0) {
+      std::fprintf(stderr, "[dialog::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. "
+                           "Integer indices would overflow.\n");
+      if (&output != input_.get()) output = *input_;
+      return;
+    }
+    check(s, c);
+    res.resize((size_t)k);
+    output.points.swap(res);
+    output.width = (uint32_t)k;
+    output.height = 1;
+    output.is_dense = true;
+    voxel_of_.assign(voe.begin(), voe.begin() + n);
+  }
+
+ private:
+  Context* ctx_;
+  PointCloudConstPtr input_;
+  std::vector<int> indices_;
+  bool has_idx_ = false;
+  dlg_voxel_params prm_{{0.f, 0.f, 0.f}, 0};
+  dlg_voxel_stats stats_{};
+  std::vector<int> voxel_of_;
+};
 
 // The fields of the reference's struct Plane (HeaderFile.h:81-88) that postProcessPlanes reads
 // and writes: points_set, coeff.values (3 = outward normal before the first post-process, 4

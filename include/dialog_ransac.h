@@ -47,7 +47,8 @@ extern "C" {
  * DLG_OPT_HYP_SHARD defaults to -1 (automatic); dlg_shard_range; dlg_cloud_signature (same ABI
  * version: an added entry); DLG_SACMODEL_PERPENDICULAR_PLANE, DLG_SACMODEL_PARALLEL_PLANE,
  * dlg_ctx_set_axis / dlg_ctx_get_axis, dlg_score_samples, dlg_axis_verdicts (same ABI version: an
- * added enum value and added entries) */
+ * added enum value and added entries); dlg_voxel_grid, dlg_voxel_grid_cloud, dlg_voxel_params,
+ * dlg_voxel_stats, DLG_OPT_VOXEL_LONG_RUN (same ABI version: added entries and an added option) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -155,7 +156,8 @@ void dlg_sac_params_default(dlg_sac_params* p);   /* PCL SACSegmentation default
 const char* dlg_status_string(dlg_status s);
 int dlg_abi_version(void);
 /* sizeof of the ABI's structs, for bindings to check their layouts: 0 dlg_points, 1 dlg_sac_params,
- * 2 dlg_sac_stats, 3 dlg_extract_stats, 4 dlg_planes, 5 dlg_postprocess_params; -1 otherwise */
+ * 2 dlg_sac_stats, 3 dlg_extract_stats, 4 dlg_planes, 5 dlg_postprocess_params, 6 dlg_voxel_params,
+ * 7 dlg_voxel_stats; -1 otherwise */
 int64_t dlg_abi_struct_size(int which);
 
 /* ---- contexts ------------------------------------------------------------------------------ */
@@ -332,6 +334,64 @@ dlg_status dlg_orient_normals_nn(dlg_ctx* ctx, const dlg_points* pts, float* nor
 dlg_status dlg_preprocess(dlg_ctx* ctx, const dlg_points* pts, int translate, float min_dist,
                           float* out_xyz, int64_t out_stride_bytes, int32_t* out_index,
                           int64_t cap, int64_t* n_out, float translation[3]);
+
+/* ---- voxel-grid downsampling (Dialog/PCLViewer.cpp:245-253, 283-300, 313-332) ---------------- */
+/* pcl::VoxelGrid<pcl::PointXYZ>::filter: the cloud replaced by one point per occupied voxel of a
+ * grid with edge lengths leaf[], the centroid of the voxel's points.  PCL 1.8's applyFilter
+ * restated from memory (parity unpinned); all arithmetic float, no contraction.
+ * The list is indices[0..n_indices) (setIndices; any order, duplicates allowed) or 0..n-1:
+ *   inv[a] = 1.0f / leaf[a]; entries with a non-finite x, y or z are skipped everywhere;
+ *   min_p / max_p = bounds of the finite entries; no finite entry: 0 voxels, DLG_OK;
+ *   (int64)((max_p[a] - min_p[a]) * inv[a]) + 1 multiplied over the axes > INT32_MAX: PCL's "Leaf
+ *   size is too small" -> DLG_ERR_INVALID, dlg_last_error "leaf size too small: voxel indices would
+ *   overflow" (PCL warns and copies the input through; the C++ shim does that).  A
+ *   floorf(min_p * inv) or floorf(max_p * inv) outside the int range: DLG_ERR_INVALID as well;
+ *   min_b[a] = (int)floorf(min_p[a] * inv[a]), max_b likewise, div[a] = max_b[a] - min_b[a] + 1;
+ *   key = ijk0 + ijk1 * div0 + ijk2 * div0 * div1 in unsigned 32-bit arithmetic, ijk[a] =
+ *   (int)(floorf(p[a] * inv[a]) - (float)min_b[a]);
+ *   the entries sorted by key; PCL's std::sort leaves the order inside a voxel unspecified, here
+ *   it is list order (a stable sort) -- sums over voxels of more than two points depend on it;
+ *   voxels of fewer than min_points_per_voxel entries are dropped;
+ *   each kept voxel, in key order: s = (0, 0, 0); s[a] += p[a] over its entries in that order
+ *   (three sequential float chains); out[a] = s[a] / (float)count.
+ * out_xyz: cap records of out_stride_bytes (12 = xyz, 16 = pcl::PointXYZ with pad 1.0f);
+ * counts_out (nullable): cap entries, the points of each output voxel; voxel_of_entry (nullable):
+ * one per list entry, its output row, or -1 when the entry is non-finite or its voxel was dropped
+ * (written whenever the call returns DLG_OK).  *n_out = output voxels, also on DLG_ERR_CAPACITY
+ * (cap too small: no output is written).  An index outside [0, pts->n), n_indices or pts->n above
+ * INT32_MAX, a leaf that is not finite and > 0, min_points_per_voxel < 0: DLG_ERR_INVALID.  One
+ * rank only: on a context of a communicator with world > 1 the points are one rank's shard, whose
+ * voxels at the cut would lose the members on other ranks (as dlg_cloud_estimate_normals):
+ * DLG_ERR_INVALID. */
+typedef struct {
+  float leaf[3];                /* setLeafSize; each finite and > 0, else DLG_ERR_INVALID */
+  int32_t min_points_per_voxel; /* setMinimumPointsNumberPerVoxel, >= 0 */
+} dlg_voxel_params;             /* dlg_abi_struct_size(6) */
+
+typedef struct {
+  int64_t n_finite;      /* entries that took part */
+  int64_t n_voxels;      /* occupied voxels before the min_points filter */
+  int32_t div[3];        /* div_b */
+  int32_t min_b[3];
+  double  device_ms;     /* HIP events around the call's device work, from the first kernel to the
+                            last (the host copies in and out excluded, the two small read-backs
+                            between included), when profiling is on; else 0 */
+} dlg_voxel_stats;       /* dlg_abi_struct_size(7) */
+
+dlg_status dlg_voxel_grid(dlg_ctx* ctx, const dlg_points* pts, const int32_t* indices,
+                          int64_t n_indices, const dlg_voxel_params* params, float* out_xyz,
+                          int64_t out_stride_bytes, int64_t cap, int64_t* n_out,
+                          int32_t* counts_out, int32_t* voxel_of_entry, dlg_voxel_stats* stats);
+/* The same filter with the result left on the device: *out is a cloud equal in every observable
+ * way to dlg_cloud_upload (indices NULL, the same id_base) of the points dlg_voxel_grid writes --
+ * the same extents, a spatial copy under the same DLG_OPT_PRUNE rule, an equal
+ * dlg_cloud_signature, global id = id_base + row -- so normals and planes can be computed on the
+ * downsampled cloud with no host round trip, and voxel_of_entry (nullable) maps them back to the
+ * input.  min_points_per_voxel applies as above.  stats nullable. */
+dlg_status dlg_voxel_grid_cloud(dlg_ctx* ctx, const dlg_points* pts, const int32_t* indices,
+                                int64_t n_indices, const dlg_voxel_params* params, int32_t id_base,
+                                dlg_cloud** out, int64_t* n_out, int32_t* voxel_of_entry,
+                                dlg_voxel_stats* stats);
 
 /* ---- postProcessPlanes (Dialog/PlaneDetect.h:1454-1579) ------------------------------------ */
 /* The final planes (plane_clouds_final, HeaderFile.h:98; struct Plane HeaderFile.h:81-88) as
@@ -601,11 +661,15 @@ enum {
                                of a chain's segment walkers to finish joins the chain's segments in
                                the walk's own launch; 0 = the joins as a launch of their own
                                (round 5).  Same sums either way */
-  DLG_OPT_UNREFINED_LIST = 23 /* lean rounds, PCL float refit: the unrefined plane's inliers in
+  DLG_OPT_UNREFINED_LIST = 23, /* lean rounds, PCL float refit: the unrefined plane's inliers in
                                list order by 1 (default) = one pass over the active list (k_ulist:
                                pristine coordinates gathered by index, look-back compaction); 0 =
                                stamps from the Morton copy's near tiles into a bitmap + its
                                compaction (rounds 3-5).  Same inliers either way */
+  DLG_OPT_VOXEL_LONG_RUN = 24 /* dlg_voxel_grid: the occupancy from which a voxel's centroid is
+                               summed by one wave (64 members loaded at a time, the chains stepped
+                               through them) instead of one thread; 1 = every voxel by a wave,
+                               INT32_MAX = none.  Default 32 (the measured cross-over).  Same bits for every value */
 };
 enum { DLG_TILE_EXACT = 0, DLG_TILE_BF16 = 1, DLG_TILE_MFMA = 2 };
 enum { DLG_SCORE_EXACT = 0, DLG_SCORE_BF16 = 1, DLG_SCORE_PRUNED = 2 };
