@@ -38,6 +38,7 @@
 
 #include "fsum.hpp"
 #include "host_math.hpp"
+#include "np_limit_host.hpp"
 #include "sac_control.hpp"
 
 namespace dlg {

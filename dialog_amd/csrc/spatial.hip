@@ -1317,22 +1317,6 @@ void launch_curv_range(const float4* nrm, int64_t n, uint32_t* out2, hipStream_t
   hipLaunchKernelGGL(k_curv_range, dim3((unsigned)blocks), dim3(256), 0, s, nrm, n, out2);
 }
 
-float np_lim_max(double w, double thr) {  // np_de_limit (np_dev.hpp) on the host
-  if (!(w >= 0.0)) return INFINITY;
-  const double omw = 1.0 - w;
-  if (!(omw > 0.0)) return INFINITY;
-  if (!(thr > 0.0)) return thr == thr ? 0.0f : NAN;
-  float x = (float)(thr / omw);
-  if (!(x == x)) return INFINITY;
-  while (!(omw * (double)x >= thr) && x < INFINITY) x = std::nextafter(x, INFINITY);
-  while (x > 0.0f) {
-    const float y = std::nextafter(x, -INFINITY);
-    if (omw * (double)y >= thr) x = y;
-    else break;
-  }
-  return x;
-}
-
 void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float cthr, float margin,
                          const float amax[3], int32_t* counts, uint16_t* lp, int32_t* lp_n,
                          int num_cus, hipStream_t s, unsigned long long* stats, const PrunedNp* np,

@@ -120,9 +120,7 @@ void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float 
                          hipEvent_t ev_start = nullptr,   // timing events of the launch pair
                          hipEvent_t ev_stop = nullptr,
                          int tile_scorer = kTileScorerExact);
-// the NORMAL_PLANE prefilter limit of the largest w (host restatement of np_de_limit): every
-// point's d_euclid limit is <= this when 0 <= w < 1 for all points; +inf otherwise
-float np_lim_max(double w_max, double thr);
+// (np_lim_max, the NORMAL_PLANE prefilter limit of the largest w: np_limit_host.hpp)
 // gather the pristine normals into the Morton-ordered copy: dst[i] = src[order[i]]
 void launch_gather_nrm(const float4* src, const int32_t* order, int64_t n, float4* dst,
                        hipStream_t s);

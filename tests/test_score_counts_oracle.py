@@ -16,8 +16,8 @@ include/dialog_ransac.h) and every count is held against three references:
   (c) an analytic count for the strict `<` at exact equality (the "slab" cloud).
 
 test_reference_is_consistent (no GPU) runs (a) through (b) and (c), so the GPU tests compare with
-a reference that was itself checked.  The SACMODEL_NORMAL_PLANE scorer has no entry point that
-returns its counts and is not covered here.
+a reference that was itself checked.  The SACMODEL_NORMAL_PLANE scorers' counts are held to the
+same three references, through dlg_score_samples, in tests/test_np_counts_oracle.py.
 """
 import ctypes as C
 import functools
