@@ -14,7 +14,8 @@ from .sac import (SAC_RANSAC, SACMODEL_NORMAL_PLANE, SACMODEL_PLANE, Cloud, Cont
 from .normals import (NormalEstimation, estimate_normals, orient_normals_nn,  # noqa: F401
                       regulate_normals)
 from .preprocess import (preprocess, remove_redundant_points, voxel_grid,  # noqa: F401
-                         voxel_grid_cloud)
+                         voxel_grid_cloud, statistical_outlier_removal,
+                         statistical_outlier_removal_cloud)
 from .postprocess import (PostProcessParams, cluster_filter, plane_border,  # noqa: F401
                           post_process_planes, refit_planes)
 from ._lib import DLG_REFIT_FAST, DLG_REFIT_PCL, LIB_PATH  # noqa: F401
@@ -23,7 +24,7 @@ from ._lib import (DLG_OPT_LEAN_ROUNDS, DLG_OPT_PCL_REFIT_DEVICE, DLG_OPT_PRUNE,
                    DLG_OPT_PRUNE_STATS, DLG_OPT_SCORE_KERNEL, DLG_OPT_SELECT_TILE,
                    DLG_OPT_REGULATE_WAVE, DLG_OPT_SPEC_PICK, DLG_OPT_FS_POISON, DLG_OPT_HYP_SHARD, DLG_OPT_FS_ONE_WALK, DLG_OPT_FS_SEGMENTS,
                    DLG_OPT_FAULT_INJECT, DLG_OPT_SYNC_CHECK, DLG_OPT_COMM_TIMEOUT_MS, DLG_OPT_SEL1_TICKET,
-                   DLG_OPT_BOUNDS_STREAM, DLG_OPT_SPATIAL_CURVE, DLG_OPT_FS_JOIN, DLG_OPT_UNREFINED_LIST, DLG_OPT_VOXEL_LONG_RUN, DLG_ERR_COMM, DLG_ERR_INTERNAL, DLG_SCORE_BF16,
+                   DLG_OPT_BOUNDS_STREAM, DLG_OPT_SPATIAL_CURVE, DLG_OPT_FS_JOIN, DLG_OPT_UNREFINED_LIST, DLG_OPT_VOXEL_LONG_RUN, DLG_OPT_SOR_LITERAL, DLG_ERR_COMM, DLG_ERR_INTERNAL, DLG_SCORE_BF16,
                    DLG_SCORE_EXACT, DLG_SCORE_PRUNED)
 
 __all__ = ["Context", "Cloud", "SACSegmentation", "extract_planes", "segment_cloud", "make_params",
@@ -32,4 +33,5 @@ __all__ = ["Context", "Cloud", "SACSegmentation", "extract_planes", "segment_clo
            "regulate_normals", "SACSegmentationFromNormals", "orient_normals_nn",
            "preprocess", "remove_redundant_points", "PostProcessParams", "post_process_planes",
            "refit_planes", "cluster_filter", "RansacControl", "SACMODEL_PERPENDICULAR_PLANE",
-           "SACMODEL_PARALLEL_PLANE", "score_samples", "voxel_grid", "voxel_grid_cloud"]
+           "SACMODEL_PARALLEL_PLANE", "score_samples", "voxel_grid", "voxel_grid_cloud",
+           "statistical_outlier_removal", "statistical_outlier_removal_cloud"]

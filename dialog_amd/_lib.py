@@ -39,6 +39,7 @@ SYMBOLS = [
     "dlg_cloud_regulate_normals", "dlg_shard_range", "dlg_cloud_signature",
     "dlg_ctx_set_axis", "dlg_ctx_get_axis", "dlg_score_samples", "dlg_axis_verdicts",
     "dlg_voxel_grid", "dlg_voxel_grid_cloud",
+    "dlg_statistical_outlier_removal", "dlg_statistical_outlier_removal_cloud",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -66,6 +67,7 @@ DLG_OPT_SPATIAL_CURVE = 21
 DLG_OPT_FS_JOIN = 22
 DLG_OPT_UNREFINED_LIST = 23
 DLG_OPT_VOXEL_LONG_RUN = 24
+DLG_OPT_SOR_LITERAL = 25
 DLG_TILE_EXACT = 0
 DLG_TILE_BF16 = 1
 DLG_TILE_MFMA = 2
@@ -98,6 +100,17 @@ class VoxelParams(C.Structure):
 class VoxelStats(C.Structure):
     _fields_ = [("n_finite", C.c_int64), ("n_voxels", C.c_int64), ("div", C.c_int32 * 3),
                 ("min_b", C.c_int32 * 3), ("device_ms", C.c_double)]
+
+
+class SorParams(C.Structure):
+    _fields_ = [("mean_k", C.c_int32), ("negative", C.c_int32), ("stddev_mul", C.c_double)]
+
+
+class SorStats(C.Structure):
+    _fields_ = [("n_finite", C.c_int64), ("n_valid", C.c_int64), ("sum", C.c_double),
+                ("sq_sum", C.c_double), ("mean", C.c_double), ("stddev", C.c_double),
+                ("threshold", C.c_double), ("literal_queries", C.c_int64),
+                ("exact_sums", C.c_int32), ("device_ms", C.c_double)]
 
 
 class SacParams(C.Structure):
@@ -225,6 +238,12 @@ def load():
     L.dlg_voxel_grid_cloud.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
                                        C.POINTER(VoxelParams), C.c_int32, pp, i64p, i32p,
                                        C.POINTER(VoxelStats)]
+    L.dlg_statistical_outlier_removal.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
+                                                  C.POINTER(SorParams), i32p, C.c_int64, i64p,
+                                                  i32p, C.c_int64, i64p, fp, C.POINTER(SorStats)]
+    L.dlg_statistical_outlier_removal_cloud.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
+                                                        C.POINTER(SorParams), C.c_int32, pp, i64p,
+                                                        i32p, C.POINTER(SorStats)]
     for s in SYMBOLS:
         if s not in ("dlg_abi_version", "dlg_status_string", "dlg_sac_params_default",
                      "dlg_last_error", "dlg_abi_struct_size"):

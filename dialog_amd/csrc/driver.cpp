@@ -159,6 +159,8 @@ int64_t dlg_abi_struct_size(int which) {
     case 5: return (int64_t)sizeof(dlg_postprocess_params);
     case 6: return (int64_t)sizeof(dlg_voxel_params);
     case 7: return (int64_t)sizeof(dlg_voxel_stats);
+    case 8: return (int64_t)sizeof(dlg_sor_params);
+    case 9: return (int64_t)sizeof(dlg_sor_stats);
   }
   return -1;
 }
@@ -279,6 +281,7 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   c->nw.release();
   c->pw.release();
   c->vw.release();
+  c->sw.release();
   c->pstats.release();
   c->sel1_status.release();
   c->sel1_err.release();
@@ -839,6 +842,7 @@ const OptRow kOptions[] = {
     OPT_BOOL(DLG_OPT_FS_JOIN, fs_join),
     OPT_BOOL(DLG_OPT_UNREFINED_LIST, unrefined_list),
     OPT(DLG_OPT_VOXEL_LONG_RUN, voxel_long_run, 1, INT32_MAX, "1..2147483647"),
+    OPT(DLG_OPT_SOR_LITERAL, sor_literal, 0, 3, "0..3"),
 };
 #undef OPT_BOOL
 #undef OPT

@@ -168,6 +168,21 @@ struct VoxelWork {
   }
 };
 
+// scratch of the statistical outlier filter (sor_host.cpp; the finite points and the hierarchy are
+// the normals path's nw.x/y/z and nw.lv[])
+struct SorWork {
+  DevBuf<uint8_t> flags, need, keep, rem;
+  DevBuf<float> ax, ay, az, dist_pt, dist;
+  DevBuf<int32_t> fin_pos, rank, sel_keep, sel_rem, out_keep, out_rem;
+  DevBuf<unsigned long long> acc;
+  void release() {
+    flags.release(); need.release(); keep.release(); rem.release();
+    ax.release(); ay.release(); az.release(); dist_pt.release(); dist.release();
+    fin_pos.release(); rank.release(); sel_keep.release(); sel_rem.release();
+    out_keep.release(); out_rem.release(); acc.release();
+  }
+};
+
 }  // namespace dlg
 
 using namespace dlg;
@@ -212,6 +227,8 @@ struct PathOptions {
   int unrefined_list = 1;   // DLG_OPT_UNREFINED_LIST: lean PCL refit's inliers by one list pass
   int voxel_long_run = 32;  // DLG_OPT_VOXEL_LONG_RUN: voxels of this many points or more are summed
                             // by one wave each (voxel.hip), smaller ones by one thread each
+  int sor_literal = 0;      // DLG_OPT_SOR_LITERAL (tests only): bit 0 every query's literal sum,
+                            // bit 1 the literal statistics loop (sor_host.cpp)
 };
 
 struct dlg_ctx {
@@ -314,6 +331,7 @@ struct dlg_ctx {
   NormalsWork nw;
   PostWork pw;
   VoxelWork vw;
+  SorWork sw;
   // PCL float refit on the device (fsum.hip): scratch sized for fs_cap inliers
   DevBuf<uint8_t> fs_scr;
   // the spatial index build's sort scratch (Morton keys and orders, ping-pong; radix-sort

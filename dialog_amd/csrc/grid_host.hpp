@@ -25,6 +25,18 @@ uint32_t build_grid(dlg_ctx* c, int n, const GridDesc& G, int lv, GridBufs* B,
                     double* pw_occ = nullptr);
 // k-nearest-neighbour grid hierarchy over nw.x/y/z
 KnnLevels build_hierarchy(dlg_ctx* c, int n, const BBox& b, int k_nn);
+// the hierarchy's plan: level 0 built (cell tuned on the occupancy), the coarser cells recorded;
+// build_level() builds a planned level on demand.  build_hierarchy_plan builds `eager_levels`
+// levels (all: -1); L.levels is the planned count either way.
+struct KnnPlan {
+  BBox b;
+  int n = 0;
+  double cell[kMaxLevels] = {};
+  int planned = 0;
+};
+void build_level(dlg_ctx* c, const KnnPlan& P, KnnLevels& L, int l, const GridBufs* B0);
+KnnLevels build_hierarchy_plan(dlg_ctx* c, int n, const BBox& b, int k_nn, KnnPlan* plan,
+                               int eager_levels);
 void check_points(const dlg_points* pts);
 
 }  // namespace dlg

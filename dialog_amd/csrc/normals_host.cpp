@@ -126,16 +126,10 @@ uint32_t build_grid(dlg_ctx* c, int n, const GridDesc& G, int lv, GridBufs* B, c
 // level-0 cell guessed from the bounding volume, then resized once from the measured occupancy
 // so an occupied cell holds ~k/2 points (surface-like clouds: occupancy ~ cell^2); levels above
 // grow 2x until one has <= 2 cells per axis
-// the hierarchy's plan: level 0 built (cell tuned on the occupancy), the coarser cells recorded;
-// build_level() builds a planned level on demand (the k-NN normals build a level only when some
-// query needs it: most clouds resolve every query within a few levels of the planned ~10)
-struct KnnPlan {
-  BBox b;
-  int n = 0;
-  double cell[kMaxLevels] = {};
-  int planned = 0;
-};
-
+// the hierarchy's plan (KnnPlan, grid_host.hpp): level 0 built (cell tuned on the occupancy), the
+// coarser cells recorded; build_level() builds a planned level on demand (the k-NN normals build a
+// level only when some query needs it: most clouds resolve every query within a few levels of the
+// planned ~10)
 void build_level(dlg_ctx* c, const KnnPlan& P, KnnLevels& L, int l, const GridBufs* B0) {
   GridBufs BL;
   GridDesc G;

@@ -83,6 +83,62 @@ def voxel_grid_cloud(points, leaf, indices=None, min_points: int = 0, id_base: i
     return res + (_voxel_stats(st),) if return_stats else res
 
 
+def _sor_args(points, mean_k, stddev_mul, indices, negative):
+    a, pts = _points(points)
+    prm = _lib.SorParams(int(mean_k), int(bool(negative)), float(stddev_mul))
+    idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.int32)
+    n = a.shape[0] if idx is None else idx.shape[0]
+    return a, pts, prm, idx, n
+
+
+def _sor_stats(st):
+    return {k: getattr(st, k) for k, _ in _lib.SorStats._fields_}
+
+
+def statistical_outlier_removal(points, mean_k: int, stddev_mul: float, indices=None,
+                                negative: bool = False, ctx: Context | None = None,
+                                return_stats: bool = False):
+    """pcl::StatisticalOutlierRemoval<PointXYZ>::filter on the GPU
+    (dlg_statistical_outlier_removal; PCLViewer.cpp:334-358): an entry is removed when the mean
+    distance to its mean_k nearest neighbours exceeds mean + stddev_mul * stddev of those means
+    (negative: when it does not).  indices: setIndices (any order, duplicates allowed); the
+    neighbours come from the whole cloud either way.  -> (kept int32 [k], removed int32 [r]: index
+    values in list order, distances float32 [n]: one per list entry) [, stats dict].  Fewer than
+    mean_k + 1 finite points raise DialogError (status 1)."""
+    ctx = ctx or default_context()
+    a, pts, prm, idx, n = _sor_args(points, mean_k, stddev_mul, indices, negative)
+    kept = np.empty(max(n, 1), np.int32)
+    rem = np.empty(max(n, 1), np.int32)
+    dist = np.empty(max(n, 1), np.float32)
+    nk, nr = C.c_int64(0), C.c_int64(0)
+    st = _lib.SorStats()
+    ctx.check(_lib.load().dlg_statistical_outlier_removal(
+        ctx.h, C.byref(pts), None if idx is None else _i32p(idx), n if idx is not None else 0,
+        C.byref(prm), _i32p(kept), n, C.byref(nk), _i32p(rem), n, C.byref(nr), _f32p(dist),
+        C.byref(st)))
+    res = (kept[:nk.value].copy(), rem[:nr.value].copy(), dist[:n].copy())
+    return res + (_sor_stats(st),) if return_stats else res
+
+
+def statistical_outlier_removal_cloud(points, mean_k: int, stddev_mul: float, indices=None,
+                                      negative: bool = False, id_base: int = 0,
+                                      ctx: Context | None = None, return_stats: bool = False):
+    """statistical_outlier_removal with the kept points left on the device
+    (dlg_statistical_outlier_removal_cloud): -> (Cloud, kept int32 [k]) [, stats dict].  The Cloud
+    equals Cloud(ctx, points[kept], id_base=id_base)."""
+    ctx = ctx or default_context()
+    a, pts, prm, idx, n = _sor_args(points, mean_k, stddev_mul, indices, negative)
+    kept = np.empty(max(n, 1), np.int32)
+    k = C.c_int64(0)
+    h = C.c_void_p()
+    st = _lib.SorStats()
+    ctx.check(_lib.load().dlg_statistical_outlier_removal_cloud(
+        ctx.h, C.byref(pts), None if idx is None else _i32p(idx), n if idx is not None else 0,
+        C.byref(prm), int(id_base), C.byref(h), C.byref(k), _i32p(kept), C.byref(st)))
+    res = (Cloud._from_handle(ctx, h, k.value), kept[:k.value].copy())
+    return res + (_sor_stats(st),) if return_stats else res
+
+
 def remove_redundant_points(points, min_dist: float, ctx: Context | None = None):
     """on_removeRedundantPointsAction_triggered (PCLViewer.cpp:781-805): -> kept indices."""
     _, idx, _ = preprocess(points, min_dist, translate=False, ctx=ctx)

@@ -16,7 +16,9 @@
 //   * regulateNormal() (PlaneDetect.h:547-665) -> dialog::regulateNormals (first round) and
 //     dialog::orientNormalsToBackup (later rounds);
 //   * preProcess() (PlaneDetect.h:448-512) -> dialog::preProcess;
-//   * pcl::VoxelGrid<PointT> (PCLViewer.cpp:245-253, 283-300, 313-332) -> dialog::VoxelGrid<PointT>.
+//   * pcl::VoxelGrid<PointT> (PCLViewer.cpp:245-253, 283-300, 313-332) -> dialog::VoxelGrid<PointT>;
+//   * pcl::StatisticalOutlierRemoval<PointT> (PCLViewer.cpp:334-358) ->
+//     dialog::StatisticalOutlierRemoval<PointT>.
 // With real PCL available define DIALOG_HAVE_PCL before including; otherwise minimal
 // layout-identical stand-ins for pcl::PointXYZ (16 B), pcl::Normal (32 B), pcl::PointCloud,
 // pcl::ModelCoefficients and pcl::PointIndices are declared here.
@@ -27,6 +29,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <memory>
@@ -420,6 +423,80 @@ class VoxelGrid {
   dlg_voxel_params prm_{{0.f, 0.f, 0.f}, 0};
   dlg_voxel_stats stats_{};
   std::vector<int> voxel_of_;
+};
+
+// pcl::StatisticalOutlierRemoval<PointT> as the reference calls it (PCLViewer.cpp:334-358):
+// setInputCloud / setMeanK / setStddevMulThresh / filter(output), plus setIndices, setNegative,
+// filter(indices) and getRemovedIndices(), on dlg_statistical_outlier_removal.  filter(output) may
+// write the cloud it reads (the reference assigns the result to source_cloud).  The neighbours
+// come from the whole input cloud whatever the index list; a cloud with fewer than mean_k + 1
+// finite points throws dialog::Error (PCL reads past FLANN's result there).
+template <typename PointT>
+class StatisticalOutlierRemoval {
+ public:
+  typedef typename pcl::PointCloud<PointT>::ConstPtr PointCloudConstPtr;
+  explicit StatisticalOutlierRemoval(Context* ctx = nullptr) : ctx_(ctx) {}
+  void setInputCloud(const PointCloudConstPtr& cloud) { input_ = cloud; }
+  void setIndices(const pcl::PointIndices::Ptr& idx) { indices_ = idx ? idx->indices : std::vector<int>(); has_idx_ = (bool)idx; }
+  void setIndices(const std::vector<int>& idx) { indices_ = idx; has_idx_ = true; }
+  void setMeanK(int k) { prm_.mean_k = k; }
+  int getMeanK() const { return prm_.mean_k; }
+  void setStddevMulThresh(double m) { prm_.stddev_mul = m; }
+  double getStddevMulThresh() const { return prm_.stddev_mul; }
+  void setNegative(bool negative) { prm_.negative = negative ? 1 : 0; }
+  bool getNegative() const { return prm_.negative != 0; }
+  const std::vector<int>& getRemovedIndices() const { return removed_; }
+  const dlg_sor_stats& lastStats() const { return stats_; }
+
+  // the kept entries' index values, in list order
+  void filter(std::vector<int>& kept) {
+    kept.clear();
+    removed_.clear();
+    stats_ = dlg_sor_stats{};
+    if (!input_) {
+      std::fprintf(stderr, "[dialog::StatisticalOutlierRemoval::filter] No input dataset given!\n");
+      return;
+    }
+    dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    dlg_points pts{input_->points.empty() ? nullptr : &input_->points[0].x,
+                   (int64_t)input_->points.size(), (int64_t)sizeof(PointT)};
+    std::vector<int32_t> idx32(indices_.begin(), indices_.end());
+    const int64_t n = has_idx_ ? (int64_t)idx32.size() : pts.n;
+    if (n == 0) return;  // (an empty index list has a null data(): the C ABI would read "no indices")
+    std::vector<int32_t> k32((size_t)n), r32((size_t)n);
+    int64_t nk = 0, nr = 0;
+    check(dlg_statistical_outlier_removal(c, &pts, has_idx_ ? idx32.data() : nullptr, n, &prm_,
+                                          k32.data(), n, &nk, r32.data(), n, &nr, nullptr, &stats_),
+          c);
+    kept.assign(k32.begin(), k32.begin() + nk);
+    removed_.assign(r32.begin(), r32.begin() + nr);
+  }
+
+  void filter(pcl::PointCloud<PointT>& output) {
+    std::vector<int> kept;
+    filter(kept);
+    std::vector<PointT> res;  // (a buffer of its own: output may be the input)
+    res.reserve(kept.size());
+    bool dense = true;
+    for (int i : kept) {
+      const PointT& p = input_->points[(size_t)i];
+      dense = dense && std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z);
+      res.push_back(p);
+    }
+    output.points.swap(res);
+    output.width = (uint32_t)output.points.size();
+    output.height = 1;
+    output.is_dense = dense;
+  }
+
+ private:
+  Context* ctx_;
+  PointCloudConstPtr input_;
+  std::vector<int> indices_;
+  bool has_idx_ = false;
+  dlg_sor_params prm_{1, 0, 0.0};
+  dlg_sor_stats stats_{};
+  std::vector<int> removed_;
 };
 
 // The fields of the reference's struct Plane (HeaderFile.h:81-88) that postProcessPlanes reads

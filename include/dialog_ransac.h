@@ -48,7 +48,9 @@ extern "C" {
  * version: an added entry); DLG_SACMODEL_PERPENDICULAR_PLANE, DLG_SACMODEL_PARALLEL_PLANE,
  * dlg_ctx_set_axis / dlg_ctx_get_axis, dlg_score_samples, dlg_axis_verdicts (same ABI version: an
  * added enum value and added entries); dlg_voxel_grid, dlg_voxel_grid_cloud, dlg_voxel_params,
- * dlg_voxel_stats, DLG_OPT_VOXEL_LONG_RUN (same ABI version: added entries and an added option) */
+ * dlg_voxel_stats, DLG_OPT_VOXEL_LONG_RUN (same ABI version: added entries and an added option);
+ * dlg_statistical_outlier_removal, dlg_statistical_outlier_removal_cloud, dlg_sor_params,
+ * dlg_sor_stats, DLG_OPT_SOR_LITERAL (same ABI version: added entries and an added option) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -157,7 +159,7 @@ const char* dlg_status_string(dlg_status s);
 int dlg_abi_version(void);
 /* sizeof of the ABI's structs, for bindings to check their layouts: 0 dlg_points, 1 dlg_sac_params,
  * 2 dlg_sac_stats, 3 dlg_extract_stats, 4 dlg_planes, 5 dlg_postprocess_params, 6 dlg_voxel_params,
- * 7 dlg_voxel_stats; -1 otherwise */
+ * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats; -1 otherwise */
 int64_t dlg_abi_struct_size(int which);
 
 /* ---- contexts ------------------------------------------------------------------------------ */
@@ -392,6 +394,63 @@ dlg_status dlg_voxel_grid_cloud(dlg_ctx* ctx, const dlg_points* pts, const int32
                                 int64_t n_indices, const dlg_voxel_params* params, int32_t id_base,
                                 dlg_cloud** out, int64_t* n_out, int32_t* voxel_of_entry,
                                 dlg_voxel_stats* stats);
+
+/* ---- statistical outlier removal (Dialog/PCLViewer.cpp:334-358) ------------------------------ */
+/* pcl::StatisticalOutlierRemoval<pcl::PointXYZ>::filter.  PCL 1.8's applyFilterIndices restated
+ * (from memory: parity unpinned) over the list indices[0..n_indices) (any
+ * order, duplicates allowed; NULL: 0..n-1):
+ *   the search structure holds every finite point of the cloud, listed or not;
+ *   a list entry with a non-finite coordinate: distances[e] = 0.0f, not counted as valid;
+ *   otherwise d2[0..mean_k] = the mean_k + 1 smallest KdTreeFLANN squared distances (float,
+ *   ((0 + dx^2) + dy^2) + dz^2) from the entry to the finite points, ascending; d2[0] (the entry
+ *   itself or a duplicate) is dropped; double s = 0; s += (double)sqrtf(d2[k]) for k = 1..mean_k;
+ *   distances[e] = (float)(s / (double)mean_k);
+ *   double sum, sq_sum over the list in order: sum += d, sq_sum += (double)(d * d) (a float product);
+ *   mean = sum / valid; variance = (sq_sum - sum * sum / valid) / (valid - 1);
+ *   threshold = mean + stddev_mul * sqrt(variance), all double (one valid entry: inf or NaN, as PCL);
+ *   entry e is removed when (double)distances[e] > threshold (negative != 0: when it is <=);
+ *   kept_out / removed_out: the index values of the kept / removed entries in list order.
+ * A NaN threshold removes nothing; non-finite entries (distance 0) are kept whenever
+ * threshold >= 0.  Where PCL reads past FLANN's result -- fewer than mean_k + 1 finite points --
+ * the call returns DLG_ERR_INVALID ("fewer than mean_k + 1 finite points"), whatever the list (an
+ * empty list over a cloud with enough finite points is DLG_OK with nothing kept).  Also DLG_ERR_INVALID:
+ * mean_k outside 1..255, a non-finite stddev_mul, an index outside [0, n), n or n_indices above
+ * INT32_MAX, a context of a communicator with world > 1 (one rank's shard lacks the neighbours
+ * across the cut, as dlg_cloud_estimate_normals).  *n_kept and *n_removed are set on
+ * DLG_ERR_CAPACITY too (a buffer too small for its list: nothing is written to it).
+ * removed_out, n_removed, distances_out (one float per list entry) and stats are nullable. */
+typedef struct {
+  int32_t mean_k;    /* setMeanK, 1..255 */
+  int32_t negative;  /* setNegative */
+  double stddev_mul; /* setStddevMulThresh, finite */
+} dlg_sor_params;    /* dlg_abi_struct_size(8) */
+
+typedef struct {
+  int64_t n_finite, n_valid;  /* finite points of the cloud; valid list entries */
+  double sum, sq_sum, mean, stddev, threshold;
+  int64_t literal_queries;    /* queries whose distance sum took the literal loop */
+  int32_t exact_sums;         /* 1: the two statistics sums were certified on the device;
+                                 0: literal host loop */
+  double device_ms;           /* HIP events around the call's device work when profiling is on
+                                 (the copies in and out excluded, the small read-backs between
+                                 included); else 0 */
+} dlg_sor_stats;              /* dlg_abi_struct_size(9) */
+
+dlg_status dlg_statistical_outlier_removal(dlg_ctx* ctx, const dlg_points* pts,
+                                           const int32_t* indices, int64_t n_indices,
+                                           const dlg_sor_params* params, int32_t* kept_out,
+                                           int64_t cap, int64_t* n_kept, int32_t* removed_out,
+                                           int64_t cap_removed, int64_t* n_removed,
+                                           float* distances_out, dlg_sor_stats* stats);
+/* The same filter with the kept points left on the device: *out is a cloud equal in every
+ * observable way to dlg_cloud_upload (indices NULL, the same id_base) of the kept points in list
+ * order -- extents, the spatial copy under the same DLG_OPT_PRUNE rule, dlg_cloud_signature, global
+ * id = id_base + row.  kept_out (nullable): room for one entry per list entry. */
+dlg_status dlg_statistical_outlier_removal_cloud(dlg_ctx* ctx, const dlg_points* pts,
+                                                 const int32_t* indices, int64_t n_indices,
+                                                 const dlg_sor_params* params, int32_t id_base,
+                                                 dlg_cloud** out, int64_t* n_kept,
+                                                 int32_t* kept_out, dlg_sor_stats* stats);
 
 /* ---- postProcessPlanes (Dialog/PlaneDetect.h:1454-1579) ------------------------------------ */
 /* The final planes (plane_clouds_final, HeaderFile.h:98; struct Plane HeaderFile.h:81-88) as
@@ -666,10 +725,14 @@ enum {
                                pristine coordinates gathered by index, look-back compaction); 0 =
                                stamps from the Morton copy's near tiles into a bitmap + its
                                compaction (rounds 3-5).  Same inliers either way */
-  DLG_OPT_VOXEL_LONG_RUN = 24 /* dlg_voxel_grid: the occupancy from which a voxel's centroid is
+  DLG_OPT_VOXEL_LONG_RUN = 24, /* dlg_voxel_grid: the occupancy from which a voxel's centroid is
                                summed by one wave (64 members loaded at a time, the chains stepped
                                through them) instead of one thread; 1 = every voxel by a wave,
                                INT32_MAX = none.  Default 32 (the measured cross-over).  Same bits for every value */
+  DLG_OPT_SOR_LITERAL = 25     /* tests only, dlg_statistical_outlier_removal: bit 0 = every
+                               query's distance sum by the literal sequential loop, bit 1 = the two
+                               statistics sums by the literal host loop.  Default 0 (either only
+                               where its certificate fails).  Same bits for every value */
 };
 enum { DLG_TILE_EXACT = 0, DLG_TILE_BF16 = 1, DLG_TILE_MFMA = 2 };
 enum { DLG_SCORE_EXACT = 0, DLG_SCORE_BF16 = 1, DLG_SCORE_PRUNED = 2 };
