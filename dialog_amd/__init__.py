@@ -15,7 +15,8 @@ from .normals import (NormalEstimation, estimate_normals, orient_normals_nn,  # 
                       regulate_normals)
 from .preprocess import (preprocess, remove_redundant_points, voxel_grid,  # noqa: F401
                          voxel_grid_cloud, statistical_outlier_removal,
-                         statistical_outlier_removal_cloud)
+                         statistical_outlier_removal_cloud, moving_least_squares,
+                         moving_least_squares_cloud)
 from .postprocess import (PostProcessParams, cluster_filter, plane_border,  # noqa: F401
                           post_process_planes, refit_planes)
 from ._lib import DLG_REFIT_FAST, DLG_REFIT_PCL, LIB_PATH  # noqa: F401
@@ -34,4 +35,5 @@ __all__ = ["Context", "Cloud", "SACSegmentation", "extract_planes", "segment_clo
            "preprocess", "remove_redundant_points", "PostProcessParams", "post_process_planes",
            "refit_planes", "cluster_filter", "RansacControl", "SACMODEL_PERPENDICULAR_PLANE",
            "SACMODEL_PARALLEL_PLANE", "score_samples", "voxel_grid", "voxel_grid_cloud",
-           "statistical_outlier_removal", "statistical_outlier_removal_cloud"]
+           "statistical_outlier_removal", "statistical_outlier_removal_cloud",
+           "moving_least_squares", "moving_least_squares_cloud"]

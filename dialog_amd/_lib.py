@@ -40,6 +40,7 @@ SYMBOLS = [
     "dlg_ctx_set_axis", "dlg_ctx_get_axis", "dlg_score_samples", "dlg_axis_verdicts",
     "dlg_voxel_grid", "dlg_voxel_grid_cloud",
     "dlg_statistical_outlier_removal", "dlg_statistical_outlier_removal_cloud",
+    "dlg_moving_least_squares", "dlg_moving_least_squares_cloud",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -111,6 +112,19 @@ class SorStats(C.Structure):
                 ("sq_sum", C.c_double), ("mean", C.c_double), ("stddev", C.c_double),
                 ("threshold", C.c_double), ("literal_queries", C.c_int64),
                 ("exact_sums", C.c_int32), ("device_ms", C.c_double)]
+
+
+class MlsParams(C.Structure):
+    _fields_ = [("search_radius", C.c_float), ("polynomial_fit", C.c_int32),
+                ("polynomial_order", C.c_int32), ("compute_normals", C.c_int32),
+                ("sqr_gauss_param", C.c_double)]
+
+
+class MlsStats(C.Structure):
+    _fields_ = [("n_finite", C.c_int64), ("n_out", C.c_int64), ("n_too_few", C.c_int64),
+                ("n_plane_only", C.c_int64), ("n_fit_nonfinite", C.c_int64),
+                ("max_neighbours", C.c_int64), ("n_lds_overflow", C.c_int64),
+                ("device_ms", C.c_double)]
 
 
 class SacParams(C.Structure):
@@ -244,6 +258,12 @@ def load():
     L.dlg_statistical_outlier_removal_cloud.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
                                                         C.POINTER(SorParams), C.c_int32, pp, i64p,
                                                         i32p, C.POINTER(SorStats)]
+    L.dlg_moving_least_squares.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
+                                           C.POINTER(MlsParams), fp, C.c_int64, fp, C.c_int64, i64p,
+                                           i32p, i32p, C.POINTER(MlsStats)]
+    L.dlg_moving_least_squares_cloud.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
+                                                 C.POINTER(MlsParams), C.c_int32, pp, i64p, i32p,
+                                                 C.POINTER(MlsStats)]
     for s in SYMBOLS:
         if s not in ("dlg_abi_version", "dlg_status_string", "dlg_sac_params_default",
                      "dlg_last_error", "dlg_abi_struct_size"):

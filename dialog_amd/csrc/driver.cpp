@@ -161,6 +161,8 @@ int64_t dlg_abi_struct_size(int which) {
     case 7: return (int64_t)sizeof(dlg_voxel_stats);
     case 8: return (int64_t)sizeof(dlg_sor_params);
     case 9: return (int64_t)sizeof(dlg_sor_stats);
+    case 10: return (int64_t)sizeof(dlg_mls_params);
+    case 11: return (int64_t)sizeof(dlg_mls_stats);
   }
   return -1;
 }
@@ -282,6 +284,7 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   c->pw.release();
   c->vw.release();
   c->sw.release();
+  c->mw.release();
   c->pstats.release();
   c->sel1_status.release();
   c->sel1_err.release();

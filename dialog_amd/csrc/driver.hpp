@@ -183,6 +183,20 @@ struct SorWork {
   }
 };
 
+// scratch of the moving-least-squares filter (mls_host.cpp; the points and the grid are the normals
+// path's nw.x/y/z and nw.lv[0])
+struct MlsWork {
+  DevBuf<uint8_t> need, valid;
+  DevBuf<float4> res_p, res_n, o_nrm;  // per point: (x, y, z, branch), (nx, ny, nz, curvature)
+  DevBuf<int32_t> lst, cnt, sel, o_src, o_nb;
+  DevBuf<float> o_xyz;
+  DevBuf<unsigned long long> acc;
+  void release() {
+    need.release(); valid.release(); res_p.release(); res_n.release(); o_nrm.release();
+    lst.release(); cnt.release(); sel.release(); o_src.release(); o_nb.release(); o_xyz.release(); acc.release();
+  }
+};
+
 }  // namespace dlg
 
 using namespace dlg;
@@ -332,6 +346,7 @@ struct dlg_ctx {
   PostWork pw;
   VoxelWork vw;
   SorWork sw;
+  MlsWork mw;
   // PCL float refit on the device (fsum.hip): scratch sized for fs_cap inliers
   DevBuf<uint8_t> fs_scr;
   // the spatial index build's sort scratch (Morton keys and orders, ping-pong; radix-sort

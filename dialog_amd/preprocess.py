@@ -139,6 +139,70 @@ def statistical_outlier_removal_cloud(points, mean_k: int, stddev_mul: float, in
     return res + (_sor_stats(st),) if return_stats else res
 
 
+def _mls_args(points, radius, order, polynomial_fit, compute_normals, sqr_gauss_param, indices):
+    a, pts = _points(points)
+    prm = _lib.MlsParams(float(radius), int(bool(polynomial_fit)), int(order),
+                         int(bool(compute_normals)), float(sqr_gauss_param))
+    idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.int32)
+    n = a.shape[0] if idx is None else idx.shape[0]
+    return a, pts, prm, idx, n
+
+
+def _mls_stats(st):
+    return {k: getattr(st, k) for k, _ in _lib.MlsStats._fields_}
+
+
+def moving_least_squares(points, radius: float, order: int = 2, polynomial_fit: bool = True,
+                         compute_normals: bool = True, sqr_gauss_param: float = 0.0, indices=None,
+                         ctx: Context | None = None, return_stats: bool = False):
+    """pcl::MovingLeastSquares<PointXYZ, PointNormal>::process on the GPU (dlg_moving_least_squares;
+    PCLViewer.cpp:387-423, "rebuild plane"): every list entry projected onto the polynomial surface
+    of degree `order` fitted to its neighbours within `radius` (polynomial_fit off, or fewer
+    neighbours than coefficients: onto their plane).  indices: setIndices (any order, duplicates
+    allowed); the neighbours come from the whole cloud either way.  sqr_gauss_param <= 0: radius^2.
+    -> (xyz float32 [k,3], normals float32 [k,4]: nx, ny, nz (not normalised, as PCL 1.8) and
+    curvature, zeros when compute_normals is off, src_index int32 [k]: each row's index value,
+    neighbours int32 [n]: one per list entry, -1 for a non-finite entry) [, stats dict].  Entries
+    that are not finite or have fewer than 3 neighbours give no row."""
+    ctx = ctx or default_context()
+    a, pts, prm, idx, n = _mls_args(points, radius, order, polynomial_fit, compute_normals,
+                                    sqr_gauss_param, indices)
+    out = np.empty((max(n, 1), 3), np.float32)
+    nrm = np.empty((max(n, 1), 4), np.float32)
+    src = np.empty(max(n, 1), np.int32)
+    nb = np.empty(max(n, 1), np.int32)
+    k = C.c_int64(0)
+    st = _lib.MlsStats()
+    ctx.check(_lib.load().dlg_moving_least_squares(
+        ctx.h, C.byref(pts), None if idx is None else _i32p(idx), n if idx is not None else 0,
+        C.byref(prm), _f32p(out), 12, _f32p(nrm), n, C.byref(k), _i32p(src), _i32p(nb),
+        C.byref(st)))
+    res = (out[:k.value].copy(), nrm[:k.value].copy(), src[:k.value].copy(), nb[:n].copy())
+    return res + (_mls_stats(st),) if return_stats else res
+
+
+def moving_least_squares_cloud(points, radius: float, order: int = 2, polynomial_fit: bool = True,
+                               compute_normals: bool = True, sqr_gauss_param: float = 0.0,
+                               indices=None, id_base: int = 0, ctx: Context | None = None,
+                               return_stats: bool = False):
+    """moving_least_squares with the smoothed points left on the device
+    (dlg_moving_least_squares_cloud): -> (Cloud, src_index int32 [k]) [, stats dict].  The Cloud
+    equals Cloud(ctx, xyz, id_base=id_base) of the rows moving_least_squares returns, with their
+    normals attached when compute_normals is on, so planes run on it with no host round trip."""
+    ctx = ctx or default_context()
+    a, pts, prm, idx, n = _mls_args(points, radius, order, polynomial_fit, compute_normals,
+                                    sqr_gauss_param, indices)
+    src = np.empty(max(n, 1), np.int32)
+    k = C.c_int64(0)
+    h = C.c_void_p()
+    st = _lib.MlsStats()
+    ctx.check(_lib.load().dlg_moving_least_squares_cloud(
+        ctx.h, C.byref(pts), None if idx is None else _i32p(idx), n if idx is not None else 0,
+        C.byref(prm), int(id_base), C.byref(h), C.byref(k), _i32p(src), C.byref(st)))
+    res = (Cloud._from_handle(ctx, h, k.value), src[:k.value].copy())
+    return res + (_mls_stats(st),) if return_stats else res
+
+
 def remove_redundant_points(points, min_dist: float, ctx: Context | None = None):
     """on_removeRedundantPointsAction_triggered (PCLViewer.cpp:781-805): -> kept indices."""
     _, idx, _ = preprocess(points, min_dist, translate=False, ctx=ctx)

@@ -18,10 +18,12 @@
 //   * preProcess() (PlaneDetect.h:448-512) -> dialog::preProcess;
 //   * pcl::VoxelGrid<PointT> (PCLViewer.cpp:245-253, 283-300, 313-332) -> dialog::VoxelGrid<PointT>;
 //   * pcl::StatisticalOutlierRemoval<PointT> (PCLViewer.cpp:334-358) ->
-//     dialog::StatisticalOutlierRemoval<PointT>.
+//     dialog::StatisticalOutlierRemoval<PointT>;
+//   * pcl::MovingLeastSquares<PointInT, PointOutT> (PCLViewer.cpp:387-423, "rebuild plane") ->
+//     dialog::MovingLeastSquares<PointInT, PointOutT>.
 // With real PCL available define DIALOG_HAVE_PCL before including; otherwise minimal
-// layout-identical stand-ins for pcl::PointXYZ (16 B), pcl::Normal (32 B), pcl::PointCloud,
-// pcl::ModelCoefficients and pcl::PointIndices are declared here.
+// layout-identical stand-ins for pcl::PointXYZ (16 B), pcl::Normal (32 B), pcl::PointNormal (48 B),
+// pcl::PointCloud, pcl::ModelCoefficients and pcl::PointIndices are declared here.
 // PCL failure behaviour is kept: segment() never throws for "no model" -- it prints an error in
 // PCL_ERROR style and leaves inliers/coefficients empty.  Device/runtime errors throw
 // dialog::Error (there is no CPU fallback).
@@ -58,6 +60,14 @@ struct alignas(16) Normal {
   float normal_x, normal_y, normal_z, data_pad;
   float curvature, pad_[3];
 };
+struct alignas(16) PointNormal {
+  float x, y, z, data_pad;
+  float normal_x, normal_y, normal_z, normal_pad;
+  float curvature, pad_[3];
+  PointNormal()
+      : x(0.f), y(0.f), z(0.f), data_pad(1.f), normal_x(0.f), normal_y(0.f), normal_z(0.f),
+        normal_pad(0.f), curvature(0.f), pad_{0.f, 0.f, 0.f} {}
+};
 template <typename T>
 struct PointCloud {
   typedef std::shared_ptr<PointCloud<T>> Ptr;
@@ -87,6 +97,7 @@ static const int SAC_RANSAC = 0;
 #endif
 
 static_assert(sizeof(pcl::PointXYZ) == 16, "pcl::PointXYZ must be 16 bytes (x, y, z, pad)");
+static_assert(sizeof(pcl::PointNormal) == 48, "pcl::PointNormal must be 48 bytes");
 static_assert((int)pcl::SACMODEL_PERPENDICULAR_PLANE == DLG_SACMODEL_PERPENDICULAR_PLANE &&
                   (int)pcl::SACMODEL_PARALLEL_PLANE == DLG_SACMODEL_PARALLEL_PLANE,
               "pcl::SacModel values are passed to the C ABI as they are");
@@ -497,6 +508,93 @@ class StatisticalOutlierRemoval {
   dlg_sor_params prm_{1, 0, 0.0};
   dlg_sor_stats stats_{};
   std::vector<int> removed_;
+};
+
+// pcl::MovingLeastSquares<PointInT, PointOutT> as the reference calls it (PCLViewer.cpp:387-423):
+// setComputeNormals / setInputCloud / setPolynomialFit / setSearchMethod (accepted and ignored: the
+// search is the library's grid) / setSearchRadius / process(output), plus setIndices,
+// setPolynomialOrder, setSqrGaussParam and getCorrespondingIndices(), on dlg_moving_least_squares
+// (upsampling NONE).  PointOutT needs x, y, z; normal_x / normal_y / normal_z / curvature are
+// written when it has them (pcl::PointNormal) and setComputeNormals(true).  The normals are not
+// normalised (PCL 1.8).  A non-finite entry and one with fewer than 3 neighbours give no point.
+template <typename PointInT, typename PointOutT>
+class MovingLeastSquares {
+ public:
+  typedef typename pcl::PointCloud<PointInT>::ConstPtr PointCloudInConstPtr;
+  explicit MovingLeastSquares(Context* ctx = nullptr) : ctx_(ctx) {}
+  void setInputCloud(const PointCloudInConstPtr& cloud) { input_ = cloud; }
+  void setIndices(const pcl::PointIndices::Ptr& idx) { indices_ = idx ? idx->indices : std::vector<int>(); has_idx_ = (bool)idx; }
+  void setIndices(const std::vector<int>& idx) { indices_ = idx; has_idx_ = true; }
+  template <typename TreePtr>
+  void setSearchMethod(const TreePtr&) {}
+  void setSearchRadius(double r) { prm_.search_radius = (float)r; sqr_gauss_set_ = false; }
+  double getSearchRadius() const { return prm_.search_radius; }
+  void setPolynomialFit(bool fit) { prm_.polynomial_fit = fit ? 1 : 0; }
+  bool getPolynomialFit() const { return prm_.polynomial_fit != 0; }
+  void setPolynomialOrder(int order) { prm_.polynomial_order = order; }
+  int getPolynomialOrder() const { return prm_.polynomial_order; }
+  // (PCL: setSearchRadius resets the parameter to radius^2; set it after the radius)
+  void setSqrGaussParam(double g) { prm_.sqr_gauss_param = g; sqr_gauss_set_ = true; }
+  double getSqrGaussParam() const {
+    return sqr_gauss_set_ ? prm_.sqr_gauss_param
+                          : (double)prm_.search_radius * (double)prm_.search_radius;
+  }
+  void setComputeNormals(bool on) { prm_.compute_normals = on ? 1 : 0; }
+  // the input index of every output point (PCL: a PointIndices::Ptr)
+  pcl::PointIndices::Ptr getCorrespondingIndices() const { return corresponding_; }
+  const dlg_mls_stats& lastStats() const { return stats_; }
+
+  void process(pcl::PointCloud<PointOutT>& output) {
+    corresponding_.reset(new pcl::PointIndices);
+    stats_ = dlg_mls_stats{};
+    output.points.clear();
+    output.width = 0;
+    output.height = 1;
+    output.is_dense = true;
+    if (!input_) {
+      std::fprintf(stderr, "[dialog::MovingLeastSquares::process] No input dataset given!\n");
+      return;
+    }
+    dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    dlg_points pts{input_->points.empty() ? nullptr : &input_->points[0].x,
+                   (int64_t)input_->points.size(), (int64_t)sizeof(PointInT)};
+    std::vector<int32_t> idx32(indices_.begin(), indices_.end());
+    const int64_t n = has_idx_ ? (int64_t)idx32.size() : pts.n;
+    if (n == 0) return;  // (an empty index list has a null data(): the C ABI would read "no indices")
+    dlg_mls_params prm = prm_;
+    if (!sqr_gauss_set_) prm.sqr_gauss_param = 0.0;
+    std::vector<float> xyz((size_t)n * 3), nrm((size_t)n * 4);
+    std::vector<int32_t> src((size_t)n);
+    int64_t k = 0;
+    check(dlg_moving_least_squares(c, &pts, has_idx_ ? idx32.data() : nullptr, n, &prm, xyz.data(),
+                                   12, nrm.data(), n, &k, src.data(), nullptr, &stats_),
+          c);
+    output.points.resize((size_t)k);
+    for (int64_t i = 0; i < k; ++i) {
+      PointOutT& o = output.points[(size_t)i];
+      o.x = xyz[3 * i]; o.y = xyz[3 * i + 1]; o.z = xyz[3 * i + 2];
+      if (prm.compute_normals) set_normal(o, &nrm[4 * i], 0);
+    }
+    output.width = (uint32_t)k;
+    corresponding_->indices.assign(src.begin(), src.begin() + k);
+  }
+
+ private:
+  template <typename P>
+  static auto set_normal(P& o, const float* r, int) -> decltype((void)o.normal_x, (void)o.curvature) {
+    o.normal_x = r[0]; o.normal_y = r[1]; o.normal_z = r[2]; o.curvature = r[3];
+  }
+  template <typename P>
+  static void set_normal(P&, const float*, long) {}
+
+  Context* ctx_;
+  PointCloudInConstPtr input_;
+  std::vector<int> indices_;
+  bool has_idx_ = false;
+  bool sqr_gauss_set_ = false;
+  dlg_mls_params prm_{0.0f, 0, 2, 0, 0.0};
+  dlg_mls_stats stats_{};
+  pcl::PointIndices::Ptr corresponding_;
 };
 
 // The fields of the reference's struct Plane (HeaderFile.h:81-88) that postProcessPlanes reads

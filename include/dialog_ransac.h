@@ -50,7 +50,9 @@ extern "C" {
  * added enum value and added entries); dlg_voxel_grid, dlg_voxel_grid_cloud, dlg_voxel_params,
  * dlg_voxel_stats, DLG_OPT_VOXEL_LONG_RUN (same ABI version: added entries and an added option);
  * dlg_statistical_outlier_removal, dlg_statistical_outlier_removal_cloud, dlg_sor_params,
- * dlg_sor_stats, DLG_OPT_SOR_LITERAL (same ABI version: added entries and an added option) */
+ * dlg_sor_stats, DLG_OPT_SOR_LITERAL (same ABI version: added entries and an added option);
+ * dlg_moving_least_squares, dlg_moving_least_squares_cloud, dlg_mls_params, dlg_mls_stats (same ABI
+ * version: added entries) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -159,7 +161,8 @@ const char* dlg_status_string(dlg_status s);
 int dlg_abi_version(void);
 /* sizeof of the ABI's structs, for bindings to check their layouts: 0 dlg_points, 1 dlg_sac_params,
  * 2 dlg_sac_stats, 3 dlg_extract_stats, 4 dlg_planes, 5 dlg_postprocess_params, 6 dlg_voxel_params,
- * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats; -1 otherwise */
+ * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats, 10 dlg_mls_params, 11 dlg_mls_stats;
+ * -1 otherwise */
 int64_t dlg_abi_struct_size(int which);
 
 /* ---- contexts ------------------------------------------------------------------------------ */
@@ -451,6 +454,71 @@ dlg_status dlg_statistical_outlier_removal_cloud(dlg_ctx* ctx, const dlg_points*
                                                  const dlg_sor_params* params, int32_t id_base,
                                                  dlg_cloud** out, int64_t* n_kept,
                                                  int32_t* kept_out, dlg_sor_stats* stats);
+
+/* ---- moving least squares (Dialog/PCLViewer.cpp:387-423, "rebuild plane") --------------------- */
+/* pcl::MovingLeastSquares<pcl::PointXYZ, pcl::PointNormal>::process with upsampling NONE.  PCL
+ * 1.8's computeMLSPointNormal restated (from memory: parity unpinned) over the
+ * list indices[0..n_indices) (any order, duplicates allowed; NULL: 0..n-1).  All arithmetic double
+ * unless marked float:
+ *   the search structure holds every finite point of the cloud, listed or not;
+ *   a list entry with a non-finite coordinate gives no output row (PCL asserts there);
+ *   the neighbours of a query q: KdTreeFLANN's radius search, float ((0 + dx^2) + dy^2) + dz^2 <
+ *   (float)((double)r * (double)r), q included; fewer than 3: no output row;
+ *   centroid = (sum p) / m; C = sum (p - centroid)(p - centroid)^T, unnormalised;
+ *   (lambda, n) = pcl::eigen33(C); d = -(n . centroid); dist = q . n + d; point = q - dist n;
+ *   curvature = trace(C), non-zero: |lambda / trace|, cast to float;
+ *   polynomial_fit != 0 and m >= nr_coeff = (order + 1)(order + 2) / 2: v = n.unitOrthogonal()
+ *   (Eigen), u = n x v; per neighbour de = p - point, sq = (float)(de . de), w = exp(-(double)sq /
+ *   sqr_gauss_param), uc = de . u, vc = de . v, f = de . n, t_j = uc^ui vc^vi (ui = 0..order, vi =
+ *   0..order - ui); A = sum (t w) t^T, b = sum (t w) f; c = A.llt().solve(b) with no success check
+ *   (Eigen's unblocked Cholesky stops at the first pivot <= 0; the solves run over what it left);
+ *   isfinite(c[0]): point += c[0] n and normal = n - c[order + 1] u - c[1] v, not normalised (PCL
+ *   1.8); otherwise the projected point and n stand.
+ * The order of the sums over the neighbours is not part of the contract.
+ * Output rows in list order: out_xyz (records of out_stride_bytes: 12 = xyz, 16 = pcl::PointXYZ with
+ * pad 1.0f), out_normals (nullable; 16-byte rows nx, ny, nz, curvature; all zero when
+ * compute_normals == 0), src_index (nullable; the row's index value, getCorrespondingIndices);
+ * neighbours (nullable): one per list entry, its neighbour count, -1 for a non-finite entry.
+ * *n_out = rows, also on DLG_ERR_CAPACITY (cap too small: no output row is written).
+ * DLG_ERR_INVALID: polynomial_order outside 1..3, a search_radius that is not finite and > 0, an
+ * index outside [0, n), n or n_indices above INT32_MAX, a context of a communicator with world > 1
+ * (one rank's shard lacks the neighbours across the cut). */
+typedef struct {
+  float search_radius;      /* setSearchRadius; finite and > 0 */
+  int32_t polynomial_fit;   /* setPolynomialFit */
+  int32_t polynomial_order; /* setPolynomialOrder, 1..3 (PCL's default: 2) */
+  int32_t compute_normals;  /* setComputeNormals */
+  double sqr_gauss_param;   /* setSqrGaussParam; <= 0: search_radius^2 (PCL's default) */
+} dlg_mls_params;           /* dlg_abi_struct_size(10) */
+
+typedef struct {
+  int64_t n_finite;         /* finite points of the cloud */
+  int64_t n_out;            /* output rows */
+  int64_t n_too_few;        /* finite list entries with fewer than 3 neighbours (no row) */
+  int64_t n_plane_only;     /* rows without a polynomial fit (polynomial_fit off or m < nr_coeff) */
+  int64_t n_fit_nonfinite;  /* rows whose fit gave a non-finite c[0]: the projection stands */
+  int64_t max_neighbours;   /* the largest neighbour count of a finite list entry */
+  int64_t n_lds_overflow;   /* finite list entries whose neighbours were read again from the grid
+                               (more than the kernel's on-chip buffer holds) */
+  double device_ms;         /* HIP events around the call's device work when profiling is on (the
+                               copies in and out excluded, the small read-backs between included) */
+} dlg_mls_stats;            /* dlg_abi_struct_size(11) */
+
+dlg_status dlg_moving_least_squares(dlg_ctx* ctx, const dlg_points* pts, const int32_t* indices,
+                                    int64_t n_indices, const dlg_mls_params* params, float* out_xyz,
+                                    int64_t out_stride_bytes, float* out_normals, int64_t cap,
+                                    int64_t* n_out, int32_t* src_index, int32_t* neighbours,
+                                    dlg_mls_stats* stats);
+/* The same filter with the result left on the device: *out is a cloud equal in every observable way
+ * to dlg_cloud_upload (indices NULL, the same id_base) of the rows dlg_moving_least_squares writes,
+ * and with compute_normals != 0 its normals are attached as dlg_cloud_set_normals would attach
+ * out_normals, so dlg_extract_planes can run (SACMODEL_NORMAL_PLANE too) with no host round trip.
+ * src_index (nullable): room for one entry per list entry. */
+dlg_status dlg_moving_least_squares_cloud(dlg_ctx* ctx, const dlg_points* pts,
+                                          const int32_t* indices, int64_t n_indices,
+                                          const dlg_mls_params* params, int32_t id_base,
+                                          dlg_cloud** out, int64_t* n_out, int32_t* src_index,
+                                          dlg_mls_stats* stats);
 
 /* ---- postProcessPlanes (Dialog/PlaneDetect.h:1454-1579) ------------------------------------ */
 /* The final planes (plane_clouds_final, HeaderFile.h:98; struct Plane HeaderFile.h:81-88) as
