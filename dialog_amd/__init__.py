@@ -17,6 +17,7 @@ from .preprocess import (preprocess, remove_redundant_points, voxel_grid,  # noq
                          voxel_grid_cloud, statistical_outlier_removal,
                          statistical_outlier_removal_cloud, moving_least_squares,
                          moving_least_squares_cloud)
+from .registration import icp_align, icp_correspondences  # noqa: F401
 from .postprocess import (PostProcessParams, cluster_filter, plane_border,  # noqa: F401
                           post_process_planes, refit_planes)
 from ._lib import DLG_REFIT_FAST, DLG_REFIT_PCL, LIB_PATH  # noqa: F401
@@ -25,7 +26,7 @@ from ._lib import (DLG_OPT_LEAN_ROUNDS, DLG_OPT_PCL_REFIT_DEVICE, DLG_OPT_PRUNE,
                    DLG_OPT_PRUNE_STATS, DLG_OPT_SCORE_KERNEL, DLG_OPT_SELECT_TILE,
                    DLG_OPT_REGULATE_WAVE, DLG_OPT_SPEC_PICK, DLG_OPT_FS_POISON, DLG_OPT_HYP_SHARD, DLG_OPT_FS_ONE_WALK, DLG_OPT_FS_SEGMENTS,
                    DLG_OPT_FAULT_INJECT, DLG_OPT_SYNC_CHECK, DLG_OPT_COMM_TIMEOUT_MS, DLG_OPT_SEL1_TICKET,
-                   DLG_OPT_BOUNDS_STREAM, DLG_OPT_SPATIAL_CURVE, DLG_OPT_FS_JOIN, DLG_OPT_UNREFINED_LIST, DLG_OPT_VOXEL_LONG_RUN, DLG_OPT_SOR_LITERAL, DLG_ERR_COMM, DLG_ERR_INTERNAL, DLG_SCORE_BF16,
+                   DLG_OPT_BOUNDS_STREAM, DLG_OPT_SPATIAL_CURVE, DLG_OPT_FS_JOIN, DLG_OPT_UNREFINED_LIST, DLG_OPT_VOXEL_LONG_RUN, DLG_OPT_SOR_LITERAL, DLG_OPT_ICP_REVERSED, DLG_ERR_COMM, DLG_ERR_INTERNAL, DLG_SCORE_BF16,
                    DLG_SCORE_EXACT, DLG_SCORE_PRUNED)
 
 __all__ = ["Context", "Cloud", "SACSegmentation", "extract_planes", "segment_cloud", "make_params",
@@ -36,4 +37,5 @@ __all__ = ["Context", "Cloud", "SACSegmentation", "extract_planes", "segment_clo
            "refit_planes", "cluster_filter", "RansacControl", "SACMODEL_PERPENDICULAR_PLANE",
            "SACMODEL_PARALLEL_PLANE", "score_samples", "voxel_grid", "voxel_grid_cloud",
            "statistical_outlier_removal", "statistical_outlier_removal_cloud",
-           "moving_least_squares", "moving_least_squares_cloud"]
+           "moving_least_squares", "moving_least_squares_cloud", "icp_align",
+           "icp_correspondences"]

@@ -41,6 +41,7 @@ SYMBOLS = [
     "dlg_voxel_grid", "dlg_voxel_grid_cloud",
     "dlg_statistical_outlier_removal", "dlg_statistical_outlier_removal_cloud",
     "dlg_moving_least_squares", "dlg_moving_least_squares_cloud",
+    "dlg_icp_params_default", "dlg_icp_align", "dlg_icp_correspondences",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -69,6 +70,13 @@ DLG_OPT_FS_JOIN = 22
 DLG_OPT_UNREFINED_LIST = 23
 DLG_OPT_VOXEL_LONG_RUN = 24
 DLG_OPT_SOR_LITERAL = 25
+DLG_OPT_ICP_REVERSED = 26
+DLG_ICP_NOT_CONVERGED = 0
+DLG_ICP_ITERATIONS = 1
+DLG_ICP_TRANSFORM = 2
+DLG_ICP_ABS_MSE = 3
+DLG_ICP_REL_MSE = 4
+DLG_ICP_NO_CORRESPONDENCES = 5
 DLG_TILE_EXACT = 0
 DLG_TILE_BF16 = 1
 DLG_TILE_MFMA = 2
@@ -125,6 +133,24 @@ class MlsStats(C.Structure):
                 ("n_plane_only", C.c_int64), ("n_fit_nonfinite", C.c_int64),
                 ("max_neighbours", C.c_int64), ("n_lds_overflow", C.c_int64),
                 ("device_ms", C.c_double)]
+
+
+class IcpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("compute_fitness", C.c_int32),
+                ("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double),
+                ("euclidean_fitness_epsilon", C.c_double), ("fitness_max_range", C.c_double)]
+
+
+class IcpStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("state", C.c_int32),
+                ("levels", C.c_int32), ("n_corr", C.c_int64), ("n_src_finite", C.c_int64),
+                ("n_tgt_finite", C.c_int64), ("host_syncs", C.c_int64), ("mse", C.c_double),
+                ("fitness", C.c_double), ("build_ms", C.c_double), ("device_ms", C.c_double)]
+
+
+class IcpIteration(C.Structure):
+    _fields_ = [("n_corr", C.c_int64), ("mse", C.c_double), ("e", C.c_int32), ("e2", C.c_int32),
+                ("T", C.c_float * 16)]
 
 
 class SacParams(C.Structure):
@@ -264,9 +290,16 @@ def load():
     L.dlg_moving_least_squares_cloud.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
                                                  C.POINTER(MlsParams), C.c_int32, pp, i64p, i32p,
                                                  C.POINTER(MlsStats)]
+    L.dlg_icp_params_default.argtypes = [C.POINTER(IcpParams)]
+    L.dlg_icp_params_default.restype = None
+    L.dlg_icp_align.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64, C.POINTER(Points),
+                                C.POINTER(IcpParams), fp, fp, fp, C.c_int64,
+                                C.POINTER(IcpIteration), C.c_int64, C.POINTER(IcpStats)]
+    L.dlg_icp_correspondences.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
+                                          C.POINTER(Points), fp, C.c_double, i32p, fp, i64p]
     for s in SYMBOLS:
         if s not in ("dlg_abi_version", "dlg_status_string", "dlg_sac_params_default",
-                     "dlg_last_error", "dlg_abi_struct_size"):
+                     "dlg_last_error", "dlg_abi_struct_size", "dlg_icp_params_default"):
             getattr(L, s).restype = C.c_int
     _lib = L
     return L

@@ -163,6 +163,10 @@ int64_t dlg_abi_struct_size(int which) {
     case 9: return (int64_t)sizeof(dlg_sor_stats);
     case 10: return (int64_t)sizeof(dlg_mls_params);
     case 11: return (int64_t)sizeof(dlg_mls_stats);
+    // (12 is left unassigned)
+    case 13: return (int64_t)sizeof(dlg_icp_params);
+    case 14: return (int64_t)sizeof(dlg_icp_stats);
+    case 15: return (int64_t)sizeof(dlg_icp_iteration);
   }
   return -1;
 }
@@ -285,6 +289,7 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   c->vw.release();
   c->sw.release();
   c->mw.release();
+  c->iw.release();
   c->pstats.release();
   c->sel1_status.release();
   c->sel1_err.release();
@@ -846,6 +851,7 @@ const OptRow kOptions[] = {
     OPT_BOOL(DLG_OPT_UNREFINED_LIST, unrefined_list),
     OPT(DLG_OPT_VOXEL_LONG_RUN, voxel_long_run, 1, INT32_MAX, "1..2147483647"),
     OPT(DLG_OPT_SOR_LITERAL, sor_literal, 0, 3, "0..3"),
+    OPT_BOOL(DLG_OPT_ICP_REVERSED, icp_reversed),
 };
 #undef OPT_BOOL
 #undef OPT

@@ -197,6 +197,22 @@ struct MlsWork {
   }
 };
 
+// scratch of the rigid registration (icp_host.cpp; the finite target points and their hierarchy are
+// the normals path's nw.x/y/z and nw.lv[])
+struct IcpWork {
+  DevBuf<uint8_t> flags, state;      // (state: one IcpState, icp.hpp)
+  DevBuf<float> tx, ty, tz, wx, wy, wz, d2;
+  DevBuf<int32_t> fin_pos, qa, qb, nn;
+  void* pub = nullptr;  // coherent pinned: k_icp_publish's copy of the state
+  void release() {
+    flags.release(); state.release(); tx.release(); ty.release(); tz.release();
+    wx.release(); wy.release(); wz.release(); d2.release();
+    fin_pos.release(); qa.release(); qb.release(); nn.release();
+    if (pub) (void)hipHostFree(pub);
+    pub = nullptr;
+  }
+};
+
 }  // namespace dlg
 
 using namespace dlg;
@@ -243,6 +259,8 @@ struct PathOptions {
                             // by one wave each (voxel.hip), smaller ones by one thread each
   int sor_literal = 0;      // DLG_OPT_SOR_LITERAL (tests only): bit 0 every query's literal sum,
                             // bit 1 the literal statistics loop (sor_host.cpp)
+  int icp_reversed = 0;     // DLG_OPT_ICP_REVERSED: the registration's level-0 pass visits W from
+                            // the last entry to the first (icp.hip)
 };
 
 struct dlg_ctx {
@@ -347,6 +365,7 @@ struct dlg_ctx {
   VoxelWork vw;
   SorWork sw;
   MlsWork mw;
+  IcpWork iw;
   // PCL float refit on the device (fsum.hip): scratch sized for fs_cap inliers
   DevBuf<uint8_t> fs_scr;
   // the spatial index build's sort scratch (Morton keys and orders, ping-pong; radix-sort

@@ -1,0 +1,310 @@
+// icp_host.cpp -- host driver of the rigid registration: dlg_icp_align and dlg_icp_correspondences
+// (include/dialog_ransac.h; pcl::IterativeClosestPoint<PointXYZ, PointXYZ> as
+// Dialog/PCLViewer.cpp:581-636 calls it).
+//
+// Once per call: the target's finite points are compacted into the normals path's nw.x/y/z and
+// their whole grid hierarchy is built; the listed source points become the working cloud W, which
+// stays on the device.  Per iteration: the level passes (the previous iteration's transformation
+// applied at level 0, deferrals counted on the device), the moments pass and the publish kernel,
+// then ONE stream synchronisation; the host runs the solve and the criteria (icp_model.hpp) and
+// the next level-0 pass takes the 16 floats as its argument.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "driver.hpp"
+#include "grid_host.hpp"
+#include "icp.hpp"
+#include "normals.hpp"
+#include "segment.hpp"  // event_ms
+
+namespace dlg {
+namespace {
+
+void check_cloud(const dlg_points* p, const char* what) {
+  if (!p || p->n < 0 || (p->n > 0 && !p->xyz))
+    throw DlgError(DLG_ERR_INVALID, std::string(what) + ": null or negative size");
+  if (p->stride_bytes < 12 || p->stride_bytes % 4)
+    throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
+  if (p->n > INT32_MAX) throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 points");
+}
+
+// max_dist^2 as the pairs are tested against it
+double squared_limit(double max_dist) {
+  if (std::isnan(max_dist) || !(max_dist > 0.0))
+    throw DlgError(DLG_ERR_INVALID, "max_correspondence_distance must be > 0");
+  const double md2 = max_dist * max_dist;
+  return md2 > DBL_MAX ? DBL_MAX : md2;
+}
+
+struct IcpCall {
+  dlg_ctx* c;
+  int m = 0;    // list entries = W's size
+  int nf = 0;   // finite target points
+  int64_t n_src_finite = 0;
+  float tmax = 0.0f;  // the target's largest finite |coordinate|
+  KnnLevels L{};
+  IcpState* st = nullptr;
+  IcpState* pub = nullptr;
+  int levels_used = 0;
+  int64_t syncs = 0;
+  double build_ms = 0.0;
+
+  explicit IcpCall(dlg_ctx* ctx) : c(ctx) {}
+
+  // the target's hierarchy and W (moved by xf when given); ev[0] is recorded behind the build
+  void setup(const dlg_points* src, const int32_t* indices, int64_t n_indices,
+             const dlg_points* tgt, const float* xf16) {
+    if (c->comm->world() > 1)
+      throw DlgError(DLG_ERR_INVALID, "registration: the target is one rank's shard (world > 1); "
+                                      "the neighbours beyond its cut need the whole cloud");
+    check_cloud(src, "source");
+    check_cloud(tgt, "target");
+    if (indices && n_indices < 0) throw DlgError(DLG_ERR_INVALID, "negative n_indices");
+    if (indices && n_indices > INT32_MAX) throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 indices");
+    m = (int)(indices ? n_indices : src->n);
+    const int64_t sf = src->stride_bytes / 4;
+    for (int i = 0; i < m; ++i) {
+      const int64_t j = indices ? indices[i] : i;
+      if (j < 0 || j >= src->n) throw DlgError(DLG_ERR_INVALID, "index out of range");
+      const float* p = src->xyz + j * sf;
+      n_src_finite += std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+    }
+    IcpXf xf{};
+    int apply = 0;
+    if (xf16) {
+      for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(xf16[k])) throw DlgError(DLG_ERR_INVALID, "the guess is not finite");
+      std::memcpy(xf.m, xf16, 64);
+      apply = !icp_is_identity(xf16);
+    }
+    if (tgt->n == 0) throw DlgError(DLG_ERR_INVALID, "the target has no finite point");
+    NormalsWork& w = c->nw;
+    IcpWork& v = c->iw;
+    const auto t0 = std::chrono::steady_clock::now();
+    // 1. the target: upload, de-interleave, the finite points, their hierarchy (every level)
+    const int nt = (int)tgt->n;
+    const size_t tbytes = (size_t)nt * (size_t)tgt->stride_bytes;
+    w.raw.ensure(tbytes);
+    HIPCHK(hipMemcpyAsync(w.raw.p, tgt->xyz, tbytes, hipMemcpyHostToDevice, c->stream));
+    v.tx.ensure(nt); v.ty.ensure(nt); v.tz.ensure(nt);
+    v.flags.ensure(nt); v.fin_pos.ensure(nt);
+    launch_deinterleave(reinterpret_cast<const float*>(w.raw.p), nt, tgt->stride_bytes / 4, v.tx.p,
+                        v.ty.p, v.tz.p, c->stream);
+    launch_finite_flags(v.tx.p, v.ty.p, v.tz.p, nt, v.flags.p, c->stream);
+    w.sort_tmp.ensure(select_tmp_bytes(nt));
+    w.counters.ensure(8);
+    w.h_cnt.ensure(8);
+    HIPCHK(select_flagged(w.sort_tmp.p, w.sort_tmp.cap, v.flags.p, nt, v.fin_pos.p, w.counters.p,
+                          c->stream));
+    HIPCHK(hipMemcpyAsync(w.h_cnt.p, w.counters.p, 4, hipMemcpyDeviceToHost, c->stream));
+    sync(c);
+    nf = (int)w.h_cnt.p[0];
+    if (nf == 0) throw DlgError(DLG_ERR_INVALID, "the target has no finite point");
+    w.x.ensure(nf); w.y.ensure(nf); w.z.ensure(nf);
+    launch_gather3(v.fin_pos.p, nf, v.tx.p, v.ty.p, v.tz.p, w.x.p, w.y.p, w.z.p, c->stream);
+    const BBox b = bbox_of(c, w.x.p, w.y.p, w.z.p, nf);
+    for (int k = 0; k < 3; ++k)
+      tmax = std::fmax(tmax, std::fmax(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
+    L = build_hierarchy(c, nf, b, 1);
+    HIPCHK(hipGetLastError());
+    if (c->profiling) {
+      sync(c);
+      build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                     .count();
+    }
+    // 2. W
+    const size_t sbytes = (size_t)src->n * (size_t)src->stride_bytes;
+    w.raw.ensure(sbytes + (indices ? 4 * (size_t)m : 0) + 16);
+    if (sbytes) HIPCHK(hipMemcpyAsync(w.raw.p, src->xyz, sbytes, hipMemcpyHostToDevice, c->stream));
+    const int32_t* didx = nullptr;
+    if (indices && m > 0) {
+      HIPCHK(hipMemcpyAsync(w.raw.p + sbytes, indices, 4 * (size_t)m, hipMemcpyHostToDevice,
+                            c->stream));
+      didx = reinterpret_cast<const int32_t*>(w.raw.p + sbytes);
+    }
+    if (c->profiling) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    const size_t mm = (size_t)std::max(m, 1);
+    v.wx.ensure(mm); v.wy.ensure(mm); v.wz.ensure(mm);
+    v.qa.ensure(mm); v.qb.ensure(mm); v.nn.ensure(mm); v.d2.ensure(mm);
+    v.state.ensure(sizeof(IcpState));
+    if (!v.pub) HIPCHK(hipHostMalloc(&v.pub, sizeof(IcpState), hipHostMallocCoherent));
+    st = reinterpret_cast<IcpState*>(v.state.p);
+    pub = reinterpret_cast<IcpState*>(v.pub);
+    HIPCHK(hipMemsetAsync(st, 0, sizeof(IcpState), c->stream));
+    launch_icp_gather(reinterpret_cast<const float*>(w.raw.p), sf, didx, m, xf, apply, v.wx.p,
+                      v.wy.p, v.wz.p, c->stream);
+    HIPCHK(hipGetLastError());
+  }
+
+  // one correspondence pass of W (first moved by xf when apply != 0) and its published sums: one
+  // stream synchronisation
+  const IcpState& pass(const IcpXf& xf, int apply, double md2) {
+    IcpWork& v = c->iw;
+    for (int l = 0; l < L.levels; ++l)
+      launch_icp_level(L, l, xf, apply, c->opt.icp_reversed, v.wx.p, v.wy.p, v.wz.p, m,
+                       (l & 1) ? v.qa.p : v.qb.p, (l & 1) ? v.qb.p : v.qa.p, st, v.fin_pos.p, md2,
+                       v.nn.p, v.d2.p, c->num_cus, c->stream);
+    launch_icp_finish(v.wx.p, v.wy.p, v.wz.p, m, v.nn.p, v.d2.p, v.tx.p, v.ty.p, v.tz.p, tmax, st,
+                      c->num_cus, c->stream);
+    launch_icp_publish(st, pub, c->stream);
+    HIPCHK(hipGetLastError());
+    sync(c);
+    ++syncs;
+    levels_used = std::max(levels_used, 1);
+    for (int l = 1; l < L.levels; ++l)
+      if (pub->qn[l] > 0) levels_used = std::max(levels_used, l + 1);
+    return *pub;
+  }
+};
+
+int64_t to_digits(const IcpState& s, int64_t* dig) {
+  for (int k = 0; k < kIcpDigits; ++k) dig[k] = (int64_t)s.dig[k];
+  return dig[0];
+}
+
+}  // namespace
+}  // namespace dlg
+
+extern "C" {
+
+void dlg_icp_params_default(dlg_icp_params* p) {
+  if (!p) return;
+  p->max_iterations = 10;
+  p->compute_fitness = 0;
+  p->max_correspondence_distance = std::sqrt(DBL_MAX);
+  p->transformation_epsilon = 0.0;
+  p->euclidean_fitness_epsilon = -DBL_MAX;
+  p->fitness_max_range = DBL_MAX;
+}
+
+dlg_status dlg_icp_align(dlg_ctx* c, const dlg_points* src, const int32_t* indices,
+                         int64_t n_indices, const dlg_points* tgt, const dlg_icp_params* prm,
+                         const float* guess, float* final_out, float* aligned_out,
+                         int64_t out_stride_bytes, dlg_icp_iteration* history_out,
+                         int64_t history_cap, dlg_icp_stats* stats) {
+  if (!c || !prm || !final_out) return DLG_ERR_INVALID;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  return guarded(c, [&] {
+    if (prm->max_iterations < 1) throw DlgError(DLG_ERR_INVALID, "max_iterations must be >= 1");
+    const double md2 = squared_limit(prm->max_correspondence_distance);
+    if (aligned_out && out_stride_bytes != 12 && out_stride_bytes != 16)
+      throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be 12 or 16");
+    if (history_out && history_cap < 0) throw DlgError(DLG_ERR_INVALID, "negative history_cap");
+    IcpCall ic(c);
+    ic.setup(src, indices, n_indices, tgt, guess);
+    IcpWork& v = c->iw;
+    float fin[16];
+    for (int k = 0; k < 16; ++k) fin[k] = guess ? guess[k] : ((k % 5 == 0) ? 1.0f : 0.0f);
+    IcpCriteria crit;
+    crit.max_iterations = prm->max_iterations;
+    crit.rot_thr = 1.0 - prm->transformation_epsilon;
+    crit.trans_thr = prm->transformation_epsilon;
+    crit.rel_mse = prm->euclidean_fitness_epsilon;
+    IcpXf xf{};       // the transformation W has not taken yet
+    int pending = 0;
+    int iterations = 0, state = kIcpNotConverged;
+    int64_t n_corr = 0;
+    double mse = 0.0;
+    int64_t dig[kIcpDigits];
+    for (;;) {
+      const IcpState& s = ic.pass(xf, pending, md2);
+      pending = 0;
+      n_corr = to_digits(s, dig);
+      if (n_corr < 3) {
+        state = kIcpNoCorrespondences;
+        break;
+      }
+      const int e = icp_qexp(std::fmax(ic.tmax, bits_float(s.wmax)));
+      const int e2 = icp_qexp(bits_float(s.d2max));
+      const IcpMoments mo = icp_moments(dig);
+      icp_solve(mo, e, e2, xf.m, &mse);
+      pending = 1;
+      icp_mul4(xf.m, fin, fin);
+      if (history_out && iterations < history_cap) {
+        dlg_icp_iteration& h = history_out[iterations];
+        h.n_corr = n_corr;
+        h.mse = mse;
+        h.e = e;
+        h.e2 = e2;
+        std::memcpy(h.T, xf.m, 64);
+      }
+      ++iterations;
+      state = icp_criteria(crit, iterations, xf.m, mse);
+      if (state != kIcpNotConverged) break;
+    }
+    const int64_t loop_syncs = ic.syncs;
+    double fitness = 0.0;
+    if (prm->compute_fitness) {
+      const double mr = prm->fitness_max_range;
+      // (d2 <= max_range is "not d2 > max_range": the pass's own test)
+      const IcpState& s = ic.pass(xf, pending, std::isnan(mr) ? -1.0 : mr);
+      pending = 0;
+      const int64_t k = to_digits(s, dig);
+      fitness = DBL_MAX;
+      if (k > 0) {
+        const IcpMoments mo = icp_moments(dig);
+        fitness = mo.D / (double)k * pow2d(icp_qexp(bits_float(s.d2max)) - kFastBits);
+      }
+    }
+    if (pending) launch_icp_apply(xf, v.wx.p, v.wy.p, v.wz.p, ic.m, c->stream);
+    if (aligned_out && ic.m > 0) {
+      const size_t obytes = (size_t)ic.m * (size_t)out_stride_bytes;
+      c->nw.out.ensure(obytes);
+      launch_icp_pack(v.wx.p, v.wy.p, v.wz.p, ic.m, reinterpret_cast<float*>(c->nw.out.p),
+                      (int)(out_stride_bytes / 4), c->stream);
+      HIPCHK(hipGetLastError());
+      if (c->profiling) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+      HIPCHK(hipMemcpyAsync(aligned_out, c->nw.out.p, obytes, hipMemcpyDeviceToHost, c->stream));
+    } else if (c->profiling) {
+      HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    }
+    HIPCHK(hipGetLastError());
+    sync(c);
+    std::memcpy(final_out, fin, 64);
+    if (stats) {
+      stats->iterations = iterations;
+      stats->converged = state != kIcpNotConverged && state != kIcpNoCorrespondences;
+      stats->state = state;
+      stats->levels = ic.levels_used;
+      stats->n_corr = n_corr;
+      stats->n_src_finite = ic.n_src_finite;
+      stats->n_tgt_finite = ic.nf;
+      stats->host_syncs = loop_syncs;
+      stats->mse = state == kIcpNoCorrespondences && iterations == 0 ? 0.0 : mse;
+      stats->fitness = fitness;
+      stats->build_ms = ic.build_ms;
+      if (c->profiling) stats->device_ms = event_ms(c, 0, 1);
+    }
+  });
+}
+
+dlg_status dlg_icp_correspondences(dlg_ctx* c, const dlg_points* src, const int32_t* indices,
+                                   int64_t n_indices, const dlg_points* tgt, const float* transform,
+                                   double max_dist, int32_t* nn_out, float* d2_out,
+                                   int64_t* n_corr) {
+  if (!c || !n_corr) return DLG_ERR_INVALID;
+  *n_corr = 0;
+  return guarded(c, [&] {
+    const double md2 = squared_limit(max_dist);
+    IcpCall ic(c);
+    ic.setup(src, indices, n_indices, tgt, transform);
+    const IcpState& s = ic.pass(IcpXf{}, 0, md2);
+    *n_corr = (int64_t)s.dig[0];
+    IcpWork& v = c->iw;
+    if (ic.m > 0 && nn_out)
+      HIPCHK(hipMemcpyAsync(nn_out, v.nn.p, 4 * (size_t)ic.m, hipMemcpyDeviceToHost, c->stream));
+    if (ic.m > 0 && d2_out)
+      HIPCHK(hipMemcpyAsync(d2_out, v.d2.p, 4 * (size_t)ic.m, hipMemcpyDeviceToHost, c->stream));
+    sync(c);
+  });
+}
+
+}  // extern "C"

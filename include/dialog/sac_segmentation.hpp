@@ -34,6 +34,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -595,6 +596,132 @@ class MovingLeastSquares {
   dlg_mls_params prm_{0.0f, 0, 2, 0, 0.0};
   dlg_mls_stats stats_{};
   pcl::PointIndices::Ptr corresponding_;
+};
+
+// A row-major 4x4 float matrix: what getFinalTransformation returns here (no Eigen): m(r, c).
+struct Matrix4f {
+  float v[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  float& operator()(int r, int c) { return v[4 * r + c]; }
+  float operator()(int r, int c) const { return v[4 * r + c]; }
+  const float* data() const { return v; }
+  static Matrix4f Identity() { return Matrix4f(); }
+};
+
+// pcl::IterativeClosestPoint<PointSource, PointTarget> as the reference calls it
+// (PCLViewer.cpp:581-636): setInputSource / setInputTarget / setMaximumIterations /
+// setMaxCorrespondenceDistance / setTransformationEpsilon / setEuclideanFitnessEpsilon /
+// align(output[, guess]) / hasConverged / getFinalTransformation / getFitnessScore, plus setIndices,
+// on dlg_icp_align.  No reciprocal correspondences and no RANSAC rejector.  getFitnessScore runs
+// the library's correspondence kernel on the aligned cloud and sums the kept squared distances
+// exactly, as dlg_icp_stats.fitness is summed.
+template <typename PointSource, typename PointTarget>
+class IterativeClosestPoint {
+ public:
+  typedef typename pcl::PointCloud<PointSource>::ConstPtr PointCloudSourceConstPtr;
+  typedef typename pcl::PointCloud<PointTarget>::ConstPtr PointCloudTargetConstPtr;
+  explicit IterativeClosestPoint(Context* ctx = nullptr) : ctx_(ctx) {
+    dlg_icp_params_default(&prm_);
+  }
+  void setInputSource(const PointCloudSourceConstPtr& cloud) { source_ = cloud; }
+  void setInputTarget(const PointCloudTargetConstPtr& cloud) { target_ = cloud; }
+  void setIndices(const pcl::PointIndices::Ptr& idx) { indices_ = idx ? idx->indices : std::vector<int>(); has_idx_ = (bool)idx; }
+  void setIndices(const std::vector<int>& idx) { indices_ = idx; has_idx_ = true; }
+  void setMaximumIterations(int n) { prm_.max_iterations = n; }
+  int getMaximumIterations() const { return prm_.max_iterations; }
+  void setMaxCorrespondenceDistance(double d) { prm_.max_correspondence_distance = d; }
+  double getMaxCorrespondenceDistance() const { return prm_.max_correspondence_distance; }
+  void setTransformationEpsilon(double e) { prm_.transformation_epsilon = e; }
+  double getTransformationEpsilon() const { return prm_.transformation_epsilon; }
+  void setEuclideanFitnessEpsilon(double e) { prm_.euclidean_fitness_epsilon = e; }
+  double getEuclideanFitnessEpsilon() const { return prm_.euclidean_fitness_epsilon; }
+  bool hasConverged() const { return stats_.converged != 0; }
+  Matrix4f getFinalTransformation() const { return final_; }
+  const dlg_icp_stats& lastStats() const { return stats_; }
+
+  void align(pcl::PointCloud<PointSource>& output) { align_impl(output, nullptr); }
+  void align(pcl::PointCloud<PointSource>& output, const Matrix4f& guess) {
+    align_impl(output, guess.data());
+  }
+
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) {
+    if (!target_ || aligned_.empty()) return std::numeric_limits<double>::max();
+    dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    const int64_t n = (int64_t)aligned_.size() / 3;
+    dlg_points src{aligned_.data(), n, 12};
+    dlg_points tgt = target_points();
+    std::vector<int32_t> nn((size_t)n);
+    std::vector<float> d2((size_t)n);
+    int64_t k = 0;
+    check(dlg_icp_correspondences(c, &src, nullptr, 0, &tgt, nullptr,
+                                  prm_default_.max_correspondence_distance, nn.data(), d2.data(), &k),
+          c);
+    float dmax = 0.0f;
+    int64_t kept = 0;
+    for (int64_t i = 0; i < n; ++i)
+      if (nn[(size_t)i] >= 0 && (double)d2[(size_t)i] <= max_range) {
+        ++kept;
+        if (d2[(size_t)i] > dmax) dmax = d2[(size_t)i];
+      }
+    if (kept == 0) return std::numeric_limits<double>::max();
+    int e2 = 0;
+    if (dmax > 0.0f) (void)std::frexp((double)dmax, &e2);
+    unsigned __int128 sum = 0;
+    for (int64_t i = 0; i < n; ++i)
+      if (nn[(size_t)i] >= 0 && (double)d2[(size_t)i] <= max_range)
+        sum += (unsigned __int128)(uint64_t)std::trunc(std::ldexp((double)d2[(size_t)i], 48 - e2));
+    return std::ldexp((double)sum / (double)kept, e2 - 48);
+  }
+
+ private:
+  dlg_points target_points() const {
+    return dlg_points{target_->points.empty() ? nullptr : &target_->points[0].x,
+                      (int64_t)target_->points.size(), (int64_t)sizeof(PointTarget)};
+  }
+  void align_impl(pcl::PointCloud<PointSource>& output, const float* guess) {
+    stats_ = dlg_icp_stats{};
+    final_ = Matrix4f();
+    aligned_.clear();
+    output.points.clear();
+    output.width = 0;
+    output.height = 1;
+    output.is_dense = true;
+    if (!source_ || !target_) {
+      std::fprintf(stderr, "[dialog::IterativeClosestPoint::align] No input source or target!\n");
+      return;
+    }
+    dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    dlg_points src{source_->points.empty() ? nullptr : &source_->points[0].x,
+                   (int64_t)source_->points.size(), (int64_t)sizeof(PointSource)};
+    dlg_points tgt = target_points();
+    std::vector<int32_t> idx32(indices_.begin(), indices_.end());
+    const int64_t n = has_idx_ ? (int64_t)idx32.size() : src.n;
+    if (has_idx_ && n == 0) return;  // (an empty index list has a null data(): the C ABI would read "no indices")
+    aligned_.resize((size_t)n * 3);
+    check(dlg_icp_align(c, &src, has_idx_ ? idx32.data() : nullptr, n, &tgt, &prm_, guess, final_.v,
+                        n > 0 ? aligned_.data() : nullptr, 12, nullptr, 0, &stats_),
+          c);
+    output.points.resize((size_t)n);
+    bool dense = true;
+    for (int64_t i = 0; i < n; ++i) {
+      PointSource& o = output.points[(size_t)i];
+      o = source_->points[(size_t)(has_idx_ ? idx32[(size_t)i] : i)];
+      o.x = aligned_[3 * i]; o.y = aligned_[3 * i + 1]; o.z = aligned_[3 * i + 2];
+      dense = dense && std::isfinite(o.x) && std::isfinite(o.y) && std::isfinite(o.z);
+    }
+    output.width = (uint32_t)n;
+    output.is_dense = dense;
+  }
+
+  Context* ctx_;
+  PointCloudSourceConstPtr source_;
+  PointCloudTargetConstPtr target_;
+  std::vector<int> indices_;
+  bool has_idx_ = false;
+  dlg_icp_params prm_{};
+  dlg_icp_params prm_default_ = [] { dlg_icp_params p; dlg_icp_params_default(&p); return p; }();
+  dlg_icp_stats stats_{};
+  Matrix4f final_;
+  std::vector<float> aligned_;
 };
 
 // The fields of the reference's struct Plane (HeaderFile.h:81-88) that postProcessPlanes reads

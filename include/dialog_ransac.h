@@ -52,7 +52,9 @@ extern "C" {
  * dlg_statistical_outlier_removal, dlg_statistical_outlier_removal_cloud, dlg_sor_params,
  * dlg_sor_stats, DLG_OPT_SOR_LITERAL (same ABI version: added entries and an added option);
  * dlg_moving_least_squares, dlg_moving_least_squares_cloud, dlg_mls_params, dlg_mls_stats (same ABI
- * version: added entries) */
+ * version: added entries); dlg_icp_align, dlg_icp_correspondences, dlg_icp_params_default,
+ * dlg_icp_params, dlg_icp_stats, dlg_icp_iteration, DLG_OPT_ICP_REVERSED (same ABI version: added
+ * entries and an added option) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -161,8 +163,8 @@ const char* dlg_status_string(dlg_status s);
 int dlg_abi_version(void);
 /* sizeof of the ABI's structs, for bindings to check their layouts: 0 dlg_points, 1 dlg_sac_params,
  * 2 dlg_sac_stats, 3 dlg_extract_stats, 4 dlg_planes, 5 dlg_postprocess_params, 6 dlg_voxel_params,
- * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats, 10 dlg_mls_params, 11 dlg_mls_stats;
- * -1 otherwise */
+ * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats, 10 dlg_mls_params, 11 dlg_mls_stats,
+ * 13 dlg_icp_params, 14 dlg_icp_stats, 15 dlg_icp_iteration (12 is unassigned); -1 otherwise */
 int64_t dlg_abi_struct_size(int which);
 
 /* ---- contexts ------------------------------------------------------------------------------ */
@@ -520,6 +522,100 @@ dlg_status dlg_moving_least_squares_cloud(dlg_ctx* ctx, const dlg_points* pts,
                                           dlg_cloud** out, int64_t* n_out, int32_t* src_index,
                                           dlg_mls_stats* stats);
 
+/* ---- rigid registration (Dialog/PCLViewer.cpp:581-636, "registration ICP") ------------------- */
+/* pcl::IterativeClosestPoint<PointXYZ, PointXYZ>::align(output, guess) of PCL 1.8, restated (from
+ * memory: parity unpinned) with no reciprocal correspondences and no RANSAC
+ * rejector; min_number_correspondences is 3.
+ *   Source: the list indices[0..n_indices) over src (any order, duplicates allowed; NULL: 0..n-1);
+ *   the target search structure holds every finite target point.  final = guess (NULL: identity);
+ *   the working cloud W = the listed source points, moved by guess unless it is bit-equal to the
+ *   identity.  A point through a row-major 4x4 m, in float without contraction:
+ *   x' = ((m00 x + m01 y) + m02 z) + m03, y' and z' alike.
+ *   One iteration:
+ *   1. every W entry with finite coordinates pairs with its nearest finite target point, float
+ *      d2 = ((0 + dx^2) + dy^2) + dz^2 (FLANN), equal distances to the lowest index; the pair is
+ *      dropped when (double)d2 > max_dist^2 (double; a product above DBL_MAX counts as DBL_MAX).
+ *      Fewer than 3 pairs: state NO_CORRESPONDENCES, converged = 0, W and final stay.
+ *   2. exact integer moments of the pairs (csrc/icp_model.hpp): e = the binary exponent with
+ *      F < 2^e, F the larger of the target's and W's largest finite |coordinate|;
+ *      q(v) = trunc(v 2^(48 - e)); m, S_a = sum q(w_a), T_a = sum q(t_a), P_ab = sum q(w_a) q(t_b);
+ *      M_ab = RN(m P_ab - S_a T_b), cs_a = RN(S_a) / m 2^(e - 48), ct alike.  No visiting order,
+ *      grouping or launch shape shows in any bit.
+ *   3. R by Horn's closed form on M (double + - * / sqrt only: a fixed cyclic Jacobi on the 4x4
+ *      N(M)), t = ct - R cs; T = (R | t) cast to float.
+ *   4. W <- T W; final <- T final (float 4x4 product, each entry's four products summed left to
+ *      right); ++iterations.
+ *   5. DefaultConvergenceCriteria in this order: iterations >= max_iterations -> ITERATIONS;
+ *      0.5 (T00 + T11 + T22 - 1) >= 1 - transformation_epsilon and |t|^2 <= transformation_epsilon
+ *      -> TRANSFORM; |mse - prev| < 1e-12 -> ABS_MSE; |mse - prev| / prev <
+ *      euclidean_fitness_epsilon -> REL_MSE; else prev = mse (DBL_MAX at first) and the loop goes
+ *      on.  mse = RN(D) / m 2^(e2 - 48), D = sum trunc(d2 2^(48 - e2)), e2 the exponent of the
+ *      iteration's largest kept d2.  The similar-transform counter of PCL is left out.
+ *   getFitnessScore(fitness_max_range) when compute_fitness != 0: one more correspondence pass of
+ *   the final W keeping d2 <= max_range, summed as the mse is; DBL_MAX when nothing is kept.
+ * DLG_ERR_INVALID: a context of a communicator with world > 1 (one rank's target shard lacks the
+ * neighbours beyond its cut), an index outside [0, n), n, n_indices or the target's n above
+ * INT32_MAX, a target with no finite point, max_iterations < 1, a non-finite guess, a
+ * max_correspondence_distance that is NaN or <= 0. */
+enum {
+  DLG_ICP_NOT_CONVERGED = 0,
+  DLG_ICP_ITERATIONS = 1,
+  DLG_ICP_TRANSFORM = 2,
+  DLG_ICP_ABS_MSE = 3,
+  DLG_ICP_REL_MSE = 4,
+  DLG_ICP_NO_CORRESPONDENCES = 5
+};
+
+typedef struct {
+  int32_t max_iterations;             /* setMaximumIterations (10) */
+  int32_t compute_fitness;            /* != 0: stats->fitness = getFitnessScore(fitness_max_range) */
+  double max_correspondence_distance; /* setMaxCorrespondenceDistance (sqrt(DBL_MAX)) */
+  double transformation_epsilon;      /* setTransformationEpsilon (0) */
+  double euclidean_fitness_epsilon;   /* setEuclideanFitnessEpsilon (-DBL_MAX) */
+  double fitness_max_range;           /* getFitnessScore's max_range (DBL_MAX) */
+} dlg_icp_params;                     /* dlg_abi_struct_size(13) */
+
+typedef struct {
+  int32_t iterations;       /* nr_iterations_ */
+  int32_t converged;        /* hasConverged */
+  int32_t state;            /* DLG_ICP_* (getConvergeCriteria()->getConvergenceState()) */
+  int32_t levels;           /* hierarchy levels a query of the call reached */
+  int64_t n_corr;           /* pairs of the last correspondence pass of the loop */
+  int64_t n_src_finite;     /* list entries whose source point is finite */
+  int64_t n_tgt_finite;     /* finite target points */
+  int64_t host_syncs;       /* stream synchronisations inside the iteration loop */
+  double mse;               /* of the last iteration */
+  double fitness;           /* compute_fitness != 0, else 0 */
+  double build_ms;          /* profiling: the one-off target hierarchy build (its read-backs included) */
+  double device_ms;         /* HIP events around the call's device work after the build when
+                               profiling is on (the copies in and out excluded, the small
+                               read-backs between included) */
+} dlg_icp_stats;            /* dlg_abi_struct_size(14) */
+
+typedef struct {
+  int64_t n_corr;
+  double mse;
+  int32_t e, e2;
+  float T[16];              /* the iteration's transformation, row-major */
+} dlg_icp_iteration;        /* dlg_abi_struct_size(15) */
+
+void dlg_icp_params_default(dlg_icp_params* p);
+/* guess (nullable): row-major 4x4.  final_out: 16 floats.  aligned_out (nullable): W, one record of
+ * out_stride_bytes (12, or 16 with pad 1.0f) per list entry.  history_out (nullable): one record
+ * per iteration, the first history_cap of them. */
+dlg_status dlg_icp_align(dlg_ctx* ctx, const dlg_points* src, const int32_t* indices,
+                         int64_t n_indices, const dlg_points* tgt, const dlg_icp_params* params,
+                         const float* guess, float* final_out, float* aligned_out,
+                         int64_t out_stride_bytes, dlg_icp_iteration* history_out,
+                         int64_t history_cap, dlg_icp_stats* stats);
+/* CorrespondenceEstimation::determineCorrespondences by the kernel the iteration runs: per list
+ * entry (moved by transform unless it is NULL or bit-equal to the identity) nn_out = the target
+ * index and d2_out, or -1 and 0 for a dropped or non-finite entry; *n_corr = the pairs kept. */
+dlg_status dlg_icp_correspondences(dlg_ctx* ctx, const dlg_points* src, const int32_t* indices,
+                                   int64_t n_indices, const dlg_points* tgt, const float* transform,
+                                   double max_dist, int32_t* nn_out, float* d2_out,
+                                   int64_t* n_corr);
+
 /* ---- postProcessPlanes (Dialog/PlaneDetect.h:1454-1579) ------------------------------------ */
 /* The final planes (plane_clouds_final, HeaderFile.h:98; struct Plane HeaderFile.h:81-88) as
  * borrowed host arrays: plane k owns points[point_offsets[k] .. point_offsets[k + 1]) (its
@@ -797,10 +893,13 @@ enum {
                                summed by one wave (64 members loaded at a time, the chains stepped
                                through them) instead of one thread; 1 = every voxel by a wave,
                                INT32_MAX = none.  Default 32 (the measured cross-over).  Same bits for every value */
-  DLG_OPT_SOR_LITERAL = 25     /* tests only, dlg_statistical_outlier_removal: bit 0 = every
+  DLG_OPT_SOR_LITERAL = 25,    /* tests only, dlg_statistical_outlier_removal: bit 0 = every
                                query's distance sum by the literal sequential loop, bit 1 = the two
                                statistics sums by the literal host loop.  Default 0 (either only
                                where its certificate fails).  Same bits for every value */
+  DLG_OPT_ICP_REVERSED = 26    /* dlg_icp_align / dlg_icp_correspondences: 1 = the correspondence
+                               pass visits the working cloud from its last entry to its first.
+                               Default 0.  Same bits for every value (the sums are exact) */
 };
 enum { DLG_TILE_EXACT = 0, DLG_TILE_BF16 = 1, DLG_TILE_MFMA = 2 };
 enum { DLG_SCORE_EXACT = 0, DLG_SCORE_BF16 = 1, DLG_SCORE_PRUNED = 2 };
