@@ -852,6 +852,7 @@ const OptRow kOptions[] = {
     OPT(DLG_OPT_VOXEL_LONG_RUN, voxel_long_run, 1, INT32_MAX, "1..2147483647"),
     OPT(DLG_OPT_SOR_LITERAL, sor_literal, 0, 3, "0..3"),
     OPT_BOOL(DLG_OPT_ICP_REVERSED, icp_reversed),
+    OPT(DLG_OPT_ICP_MAX_BLOCKS, icp_max_blocks, 0, 65536, "0..65536"),
 };
 #undef OPT_BOOL
 #undef OPT

@@ -261,6 +261,8 @@ struct PathOptions {
                             // bit 1 the literal statistics loop (sor_host.cpp)
   int icp_reversed = 0;     // DLG_OPT_ICP_REVERSED: the registration's level-0 pass visits W from
                             // the last entry to the first (icp.hip)
+  int icp_max_blocks = 0;   // DLG_OPT_ICP_MAX_BLOCKS (tests only): n >= 1 caps the workgroups of
+                            // every launch of the registration (icp.hip); 0 the default shapes
 };
 
 struct dlg_ctx {

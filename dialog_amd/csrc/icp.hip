@@ -198,28 +198,37 @@ __global__ __launch_bounds__(kBS) void k_icp_pack(const float* __restrict__ wx,
   }
 }
 
-inline int stream_grid(int m) { return std::max(1, std::min(cdiv_i(m, kBS), 2048)); }
+// DLG_OPT_ICP_MAX_BLOCKS: at most max_blocks workgroups when it is >= 1 (0: the default shape)
+inline int capped(int grid, int max_blocks) {
+  return max_blocks >= 1 ? std::min(grid, max_blocks) : grid;
+}
+inline int stream_grid(int m, int max_blocks) {
+  return capped(std::max(1, std::min(cdiv_i(m, kBS), 2048)), max_blocks);
+}
 
 }  // namespace
 
 void launch_icp_gather(const float* raw, int64_t stride_f, const int32_t* idx, int m, const IcpXf& xf,
-                       int apply, float* wx, float* wy, float* wz, hipStream_t s) {
+                       int apply, float* wx, float* wy, float* wz, int max_blocks, hipStream_t s) {
   if (m <= 0) return;
-  hipLaunchKernelGGL(k_icp_gather, dim3(stream_grid(m)), dim3(kBS), 0, s, raw, stride_f, idx, m, xf,
-                     apply, wx, wy, wz);
+  hipLaunchKernelGGL(k_icp_gather, dim3(stream_grid(m, max_blocks)), dim3(kBS), 0, s, raw, stride_f,
+                     idx, m, xf, apply, wx, wy, wz);
 }
 
-void launch_icp_apply(const IcpXf& xf, float* wx, float* wy, float* wz, int m, hipStream_t s) {
+void launch_icp_apply(const IcpXf& xf, float* wx, float* wy, float* wz, int m, int max_blocks,
+                      hipStream_t s) {
   if (m <= 0) return;
-  hipLaunchKernelGGL(k_icp_apply, dim3(stream_grid(m)), dim3(kBS), 0, s, xf, wx, wy, wz, m);
+  hipLaunchKernelGGL(k_icp_apply, dim3(stream_grid(m, max_blocks)), dim3(kBS), 0, s, xf, wx, wy, wz,
+                     m);
 }
 
 void launch_icp_level(const KnnLevels& L, int level, const IcpXf& xf, int apply, int reversed,
                       float* wx, float* wy, float* wz, int m, const int32_t* qin, int32_t* qout,
                       IcpState* st, const int32_t* fin_pos, double md2, int32_t* nn, float* d2,
-                      int num_cus, hipStream_t s) {
+                      int num_cus, int max_blocks, hipStream_t s) {
   if (m <= 0) return;
-  const int grid = std::max(1, std::min(cdiv_i(m, kBS), std::max(num_cus, 1) * 8));
+  const int grid =
+      capped(std::max(1, std::min(cdiv_i(m, kBS), std::max(num_cus, 1) * 8)), max_blocks);
   if (level == 0)
     hipLaunchKernelGGL(k_icp_level<true>, dim3(grid), dim3(kBS), 0, s, L, level, xf, apply, reversed,
                        wx, wy, wz, m, qin, qout, st, fin_pos, md2, nn, d2);
@@ -230,11 +239,12 @@ void launch_icp_level(const KnnLevels& L, int level, const IcpXf& xf, int apply,
 
 void launch_icp_finish(const float* wx, const float* wy, const float* wz, int m, const int32_t* nn,
                        const float* d2, const float* tx, const float* ty, const float* tz, float tmax,
-                       IcpState* st, int num_cus, hipStream_t s) {
+                       IcpState* st, int num_cus, int max_blocks, hipStream_t s) {
   if (m <= 0) return;
   // kIcpFlush entries a thread, at least enough workgroups to fill the device, 65536 at most
   const int need = std::min(cdiv_i(m, (int64_t)kBS * kIcpFlush), 65536);
-  const int grid = std::max(1, std::min(cdiv_i(m, kBS), std::max(std::max(num_cus, 1) * 4, need)));
+  const int grid = capped(
+      std::max(1, std::min(cdiv_i(m, kBS), std::max(std::max(num_cus, 1) * 4, need))), max_blocks);
   hipLaunchKernelGGL(k_icp_finish, dim3(grid), dim3(kBS), 0, s, wx, wy, wz, m, nn, d2, tx, ty, tz,
                      tmax, st);
 }
@@ -244,9 +254,10 @@ void launch_icp_publish(IcpState* st, IcpState* pub, hipStream_t s) {
 }
 
 void launch_icp_pack(const float* wx, const float* wy, const float* wz, int m, float* out,
-                     int stride_f, hipStream_t s) {
+                     int stride_f, int max_blocks, hipStream_t s) {
   if (m <= 0) return;
-  hipLaunchKernelGGL(k_icp_pack, dim3(stream_grid(m)), dim3(kBS), 0, s, wx, wy, wz, m, out, stride_f);
+  hipLaunchKernelGGL(k_icp_pack, dim3(stream_grid(m, max_blocks)), dim3(kBS), 0, s, wx, wy, wz, m, out,
+                     stride_f);
 }
 
 }  // namespace dlg

@@ -140,7 +140,7 @@ struct IcpCall {
     pub = reinterpret_cast<IcpState*>(v.pub);
     HIPCHK(hipMemsetAsync(st, 0, sizeof(IcpState), c->stream));
     launch_icp_gather(reinterpret_cast<const float*>(w.raw.p), sf, didx, m, xf, apply, v.wx.p,
-                      v.wy.p, v.wz.p, c->stream);
+                      v.wy.p, v.wz.p, c->opt.icp_max_blocks, c->stream);
     HIPCHK(hipGetLastError());
   }
 
@@ -151,9 +151,9 @@ struct IcpCall {
     for (int l = 0; l < L.levels; ++l)
       launch_icp_level(L, l, xf, apply, c->opt.icp_reversed, v.wx.p, v.wy.p, v.wz.p, m,
                        (l & 1) ? v.qa.p : v.qb.p, (l & 1) ? v.qb.p : v.qa.p, st, v.fin_pos.p, md2,
-                       v.nn.p, v.d2.p, c->num_cus, c->stream);
+                       v.nn.p, v.d2.p, c->num_cus, c->opt.icp_max_blocks, c->stream);
     launch_icp_finish(v.wx.p, v.wy.p, v.wz.p, m, v.nn.p, v.d2.p, v.tx.p, v.ty.p, v.tz.p, tmax, st,
-                      c->num_cus, c->stream);
+                      c->num_cus, c->opt.icp_max_blocks, c->stream);
     launch_icp_publish(st, pub, c->stream);
     HIPCHK(hipGetLastError());
     sync(c);
@@ -254,12 +254,13 @@ dlg_status dlg_icp_align(dlg_ctx* c, const dlg_points* src, const int32_t* indic
         fitness = mo.D / (double)k * pow2d(icp_qexp(bits_float(s.d2max)) - kFastBits);
       }
     }
-    if (pending) launch_icp_apply(xf, v.wx.p, v.wy.p, v.wz.p, ic.m, c->stream);
+    if (pending)
+      launch_icp_apply(xf, v.wx.p, v.wy.p, v.wz.p, ic.m, c->opt.icp_max_blocks, c->stream);
     if (aligned_out && ic.m > 0) {
       const size_t obytes = (size_t)ic.m * (size_t)out_stride_bytes;
       c->nw.out.ensure(obytes);
       launch_icp_pack(v.wx.p, v.wy.p, v.wz.p, ic.m, reinterpret_cast<float*>(c->nw.out.p),
-                      (int)(out_stride_bytes / 4), c->stream);
+                      (int)(out_stride_bytes / 4), c->opt.icp_max_blocks, c->stream);
       HIPCHK(hipGetLastError());
       if (c->profiling) HIPCHK(hipEventRecord(c->ev[1], c->stream));
       HIPCHK(hipMemcpyAsync(aligned_out, c->nw.out.p, obytes, hipMemcpyDeviceToHost, c->stream));

@@ -54,7 +54,7 @@ extern "C" {
  * dlg_moving_least_squares, dlg_moving_least_squares_cloud, dlg_mls_params, dlg_mls_stats (same ABI
  * version: added entries); dlg_icp_align, dlg_icp_correspondences, dlg_icp_params_default,
  * dlg_icp_params, dlg_icp_stats, dlg_icp_iteration, DLG_OPT_ICP_REVERSED (same ABI version: added
- * entries and an added option) */
+ * entries and an added option); DLG_OPT_ICP_MAX_BLOCKS (same ABI version: an added option) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -552,7 +552,8 @@ dlg_status dlg_moving_least_squares_cloud(dlg_ctx* ctx, const dlg_points* pts,
  *      on.  mse = RN(D) / m 2^(e2 - 48), D = sum trunc(d2 2^(48 - e2)), e2 the exponent of the
  *      iteration's largest kept d2.  The similar-transform counter of PCL is left out.
  *   getFitnessScore(fitness_max_range) when compute_fitness != 0: one more correspondence pass of
- *   the final W keeping d2 <= max_range, summed as the mse is; DBL_MAX when nothing is kept.
+ *   the final W keeping d2 <= max_range, summed as the mse is; DBL_MAX when nothing is kept (a NaN
+ *   or a negative max_range keeps nothing).
  * DLG_ERR_INVALID: a context of a communicator with world > 1 (one rank's target shard lacks the
  * neighbours beyond its cut), an index outside [0, n), n, n_indices or the target's n above
  * INT32_MAX, a target with no finite point, max_iterations < 1, a non-finite guess, a
@@ -897,9 +898,15 @@ enum {
                                query's distance sum by the literal sequential loop, bit 1 = the two
                                statistics sums by the literal host loop.  Default 0 (either only
                                where its certificate fails).  Same bits for every value */
-  DLG_OPT_ICP_REVERSED = 26    /* dlg_icp_align / dlg_icp_correspondences: 1 = the correspondence
+  DLG_OPT_ICP_REVERSED = 26,   /* dlg_icp_align / dlg_icp_correspondences: 1 = the correspondence
                                pass visits the working cloud from its last entry to its first.
                                Default 0.  Same bits for every value (the sums are exact) */
+  DLG_OPT_ICP_MAX_BLOCKS = 27  /* tests only, dlg_icp_align / dlg_icp_correspondences: n >= 1 = every
+                               launch of the registration (gather, apply, level, moments, pack) runs
+                               min(its default, n) workgroups, so that a small cloud takes the
+                               several-entries-per-thread paths of a huge one; 0..65536.  Default 0
+                               (the default launch shapes).  Same bits for every value (the sums
+                               are exact) */
 };
 enum { DLG_TILE_EXACT = 0, DLG_TILE_BF16 = 1, DLG_TILE_MFMA = 2 };
 enum { DLG_SCORE_EXACT = 0, DLG_SCORE_BF16 = 1, DLG_SCORE_PRUNED = 2 };

@@ -65,6 +65,58 @@ def correspondences(W, tgt, max_dist=math.sqrt(DBL_MAX), md2=None):
     return nn, d2
 
 
+# correspondences_fast: a candidate set is certified when the 4th candidate's squared distance (double)
+# exceeds the float32 minimum by this relative margin.  A float32 d2 of normal terms carries a few
+# 2^-24 (6e-8) of relative error, so the margin is more than 100 x its rounding; below
+# FAST_D2_FLOOR the terms may be subnormal, their error is absolute, and nothing is certified.
+FAST_MARGIN = 1e-5
+FAST_D2_FLOOR = 2.0 ** -100
+FAST_K = 4
+
+
+def correspondences_fast(W, tgt, max_dist=math.sqrt(DBL_MAX), md2=None, info=None):
+    """correspondences() with a k-d tree proposing FAST_K candidates per query (double), their d2
+    re-evaluated in float32 in FLANN's operation order, the minimum taken with ties to the lowest
+    index; every query whose candidate set is not certified (see FAST_MARGIN) is answered by the
+    brute force over the whole target.  info (a dict): 'uncertified' = how many went that way."""
+    from scipy.spatial import cKDTree
+    W = np.asarray(W, f32).reshape(-1, 3)
+    tgt = np.asarray(tgt, f32).reshape(-1, 3)
+    md2 = squared_limit(max_dist) if md2 is None else md2
+    fin_t = np.nonzero(np.isfinite(tgt).all(axis=1))[0]
+    tf = tgt[fin_t]
+    nn = np.full(len(W), -1, np.int32)
+    d2 = np.zeros(len(W), f32)
+    fin_w = np.nonzero(np.isfinite(W).all(axis=1))[0]
+    slow = fin_w
+    if len(tf) > FAST_K and len(fin_w):
+        q = W[fin_w]
+        dd, cand = cKDTree(tf.astype(np.float64)).query(q.astype(np.float64), k=FAST_K)
+        with np.errstate(all="ignore"):
+            c = tf[cand]                                        # [m, K, 3] float32
+            dx = q[:, None, 0] - c[:, :, 0]
+            dy = q[:, None, 1] - c[:, :, 1]
+            dz = q[:, None, 2] - c[:, :, 2]
+            d = ((f32(0) + dx * dx) + dy * dy) + dz * dz
+            dmin = d.min(axis=1)
+            # the lowest index among the candidates at the minimum
+            j = np.where(d == dmin[:, None], cand, np.iinfo(np.int64).max).min(axis=1)
+            fm = dmin.astype(np.float64)
+            sure = (fm >= FAST_D2_FLOOR) & np.isfinite(fm) & \
+                (dd[:, FAST_K - 1] * dd[:, FAST_K - 1] > fm * (1.0 + FAST_MARGIN))
+        keep = sure & ~(fm > md2)
+        nn[fin_w[keep]] = fin_t[j[keep]]
+        d2[fin_w[keep]] = dmin[keep]
+        slow = fin_w[~sure]
+    if info is not None:
+        info["uncertified"] = info.get("uncertified", 0) + int(len(slow))
+        info["queries"] = info.get("queries", 0) + int(len(fin_w))
+    if len(slow):
+        sn, sd = correspondences(W[slow], tgt, md2=md2)
+        nn[slow], d2[slow] = sn, sd
+    return nn, d2
+
+
 def qexp(f):
     f = float(f)
     if not (f > 0.0) or not (f < math.inf):
@@ -257,9 +309,13 @@ class Criteria:
         return NOT_CONVERGED
 
 
-def fitness_score(W, tgt, max_range=DBL_MAX):
-    nn, d2 = correspondences(W, tgt, md2=float(max_range))
-    k = nn >= 0
+def fitness_score(W, tgt, max_range=DBL_MAX, fast=False, info=None):
+    """getFitnessScore: the pairs with d2 <= max_range (a NaN or negative range keeps none)"""
+    if fast:
+        nn, d2 = correspondences_fast(W, tgt, info=info)
+    else:
+        nn, d2 = correspondences(W, tgt)
+    k = (nn >= 0) & (d2.astype(np.float64) <= float(max_range))
     if not k.any():
         return DBL_MAX
     e2 = qexp(d2[k].max())
@@ -268,8 +324,10 @@ def fitness_score(W, tgt, max_range=DBL_MAX):
 
 def align(src, tgt, indices=None, guess=None, max_iterations=10, max_dist=math.sqrt(DBL_MAX),
           transformation_epsilon=0.0, euclidean_fitness_epsilon=-DBL_MAX, fitness_max_range=DBL_MAX,
-          keep_pairs=False):
-    """-> dict(final [4,4] f32, history (list of dict n_corr, mse, e, e2, T), aligned [m,3] f32,
+          keep_pairs=False, compute_fitness=True, fast=False, info=None):
+    """fast: the correspondences by correspondences_fast (info collects its counts);
+    compute_fitness False: fitness 0.0, as the library reports it when it is not asked for.
+    -> dict(final [4,4] f32, history (list of dict n_corr, mse, e, e2, T), aligned [m,3] f32,
     state, iterations, converged, fitness, n_corr, mse[, pairs: per iteration (w, t, d2)])"""
     src = np.asarray(src, f32).reshape(-1, 3)
     tgt = np.asarray(tgt, f32).reshape(-1, 3)
@@ -283,7 +341,8 @@ def align(src, tgt, indices=None, guess=None, max_iterations=10, max_dist=math.s
     hist, pairs = [], []
     iterations, state, n_corr, mse = 0, NOT_CONVERGED, 0, 0.0
     while True:
-        nn, d2 = correspondences(W, tgt, max_dist)
+        nn, d2 = correspondences_fast(W, tgt, max_dist, info=info) if fast else \
+            correspondences(W, tgt, max_dist)
         k = np.nonzero(nn >= 0)[0]
         n_corr = len(k)
         if n_corr < 3:
@@ -305,7 +364,8 @@ def align(src, tgt, indices=None, guess=None, max_iterations=10, max_dist=math.s
             break
     out = dict(final=final, history=hist, aligned=W, state=state, iterations=iterations,
                converged=int(state not in (NOT_CONVERGED, NO_CORRESPONDENCES)), n_corr=n_corr,
-               mse=mse, fitness=fitness_score(W, tgt, fitness_max_range))
+               mse=mse, fitness=fitness_score(W, tgt, fitness_max_range, fast, info)
+               if compute_fitness else 0.0)
     if keep_pairs:
         out["pairs"] = pairs
     return out
@@ -407,6 +467,90 @@ ALIGN_KEYS = ("indices", "guess", "max_iterations", "max_dist", "transformation_
 def run_case(case, **kw):
     args = {k: case[k] for k in ALIGN_KEYS if k in case}
     return align(case["src"], case["tgt"], **args, **kw)
+
+
+# ---- inputs beyond the fixture (deterministic, generated: test_icp.py checks what each is for, ----
+# ---- test_icp_gpu.py runs them on the device) -----------------------------------------------------
+def neighbour_spacing(P):
+    """the median distance of a point of P to its nearest other point (float64)"""
+    from scipy.spatial import cKDTree
+    P = np.asarray(P, np.float64)
+    return float(np.median(cKDTree(P).query(P, k=2)[0][:, 1]))
+
+
+def tiled_source(src, n, seed=4096):
+    """n entries: src repeated, every entry moved by its own float32 jitter of up to a quarter of
+    src's neighbour spacing per axis (no two entries equal)"""
+    src = np.asarray(src, f32).reshape(-1, 3)
+    j = 0.25 * neighbour_spacing(src)
+    rng = np.random.default_rng(seed)
+    return (src[np.arange(n) % len(src)] + rng.uniform(-j, j, size=(n, 3)).astype(f32)).astype(f32)
+
+
+SCATTER_RUNGS = 11          # push distances spacing * 2^0 .. 2^10
+# the share of each rung: a tenth stays within the neighbour spacing, the rungs between thin the
+# deferral queues out level by level, and more than half leave the target's extent altogether
+# (so the median d2 lies on rung 9 and the pairs below it span rungs 0..9)
+SCATTER_SHARES = [0.10] + [0.04] * 8 + [0.29, 0.29]
+
+
+def scatter_case(n_src=2987, n_tgt=3001, n_bad=8, seed=31337):
+    """dict(src, tgt, spacing): each finite source entry is a target point pushed off in a random
+    direction by spacing * 2^rung, n_bad more entries are not finite, and the list is shuffled"""
+    from dialog_amd.synth import plane_cloud
+    tgt = plane_cloud(n_tgt, 3, seed=seed, patch=2.0)[0]
+    s = neighbour_spacing(tgt)
+    rng = np.random.default_rng(seed + 1)
+    rung = rng.choice(SCATTER_RUNGS, size=n_src, p=SCATTER_SHARES)
+    u = rng.normal(size=(n_src, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    base = tgt[rng.integers(0, n_tgt, size=n_src)].astype(np.float64)
+    src = (base + u * (s * np.exp2(rung))[:, None]).astype(f32)
+    bad = np.zeros((n_bad, 3), f32)
+    bad[:] = tgt[:n_bad]
+    for k in range(n_bad):
+        bad[k, k % 3] = (np.nan, np.inf, -np.inf)[k % 3]
+    src = np.concatenate([src, bad])
+    return dict(src=np.ascontiguousarray(src[rng.permutation(len(src))]), tgt=tgt, spacing=s)
+
+
+def degenerate_cases():
+    """name -> dict(src, tgt): a target on the exact plane z = 0.25 under a source on z = 0.26, and a
+    target on the x axis (y = z = 0 exactly) beside a source a little off it"""
+    rng = np.random.default_rng(2025)
+    pt = np.empty((401, 3), f32)
+    pt[:, :2] = rng.uniform(0.0, 1.0, size=(401, 2))
+    pt[:, 2] = f32(0.25)
+    ps = np.empty((333, 3), f32)
+    ps[:, :2] = rng.uniform(0.1, 0.9, size=(333, 2))
+    ps[:, 2] = f32(0.26)
+    ps = transform_points(rigid((0, 0, 1), 2.0, (0.01, -0.02, 0.0)), ps)
+    lt = np.zeros((307, 3), f32)
+    lt[:, 0] = rng.uniform(0.0, 1.0, size=307)
+    ls = np.empty((259, 3), f32)
+    ls[:, 0] = rng.uniform(0.05, 0.9, size=259)
+    ls[:, 1:] = rng.uniform(-0.01, 0.01, size=(259, 2))
+    return dict(plane=dict(src=ps, tgt=pt), line=dict(src=ls, tgt=lt))
+
+
+SCALE_RUNGS = (-70, -60, -40, 40, 60)
+
+
+def scaled_case(case, k):
+    """the case's clouds times 2^k (exact in float32)"""
+    return dict(src=np.ldexp(case["src"], k).astype(f32), tgt=np.ldexp(case["tgt"], k).astype(f32))
+
+
+LARGE_SRC, LARGE_TGT = 600000, 50000
+
+
+def large_case():
+    """planes_iter's construction at a production launch shape: 600,000 entries against 50,000"""
+    from dialog_amd.synth import plane_cloud
+    ps = plane_cloud(LARGE_SRC, 3, seed=771, shard=0)[0]
+    pt = transform_points(rigid((0.3, -0.2, 1.0), 1.5, (0.05, -0.03, 0.02)),
+                          plane_cloud(LARGE_TGT, 3, seed=771, shard=1)[0])
+    return dict(src=ps, tgt=pt, max_iterations=2)
 
 
 def history_arrays(r):

@@ -53,6 +53,18 @@ def test_params_defaults_match_pcl():
     assert L.dlg_status_string(0) == b"ok"
 
 
+def test_option_ids_match_the_header():
+    """every DLG_OPT_* of the header has the same value in the binding, and the package exports it"""
+    src = open(os.path.join(ROOT, "include", "dialog_ransac.h")).read()
+    ids = {k: int(v) for k, v in re.findall(r"\b(DLG_OPT_[A-Z0-9_]+)\s*=\s*(\d+)", src)}
+    assert len(ids) >= 27 and len(set(ids.values())) == len(ids)
+    assert ids["DLG_OPT_ICP_REVERSED"] == 26 and ids["DLG_OPT_ICP_MAX_BLOCKS"] == 27
+    assert max(ids.values()) == 27
+    for name, v in ids.items():
+        assert getattr(_lib, name) == v, name
+        assert getattr(dialog_amd, name) == v, name
+
+
 def test_struct_layouts_match_the_header():
     """The ctypes structs have the header's sizes (dlg_abi_struct_size reports sizeof of each): a
     binding built for another layout would read or write past the caller's struct."""

@@ -2,7 +2,9 @@
 tests/icp_ref.py, the host side of dialog_amd/csrc/icp_model.hpp (a stand-alone program under
 -fsanitize=address,undefined) bit-equal to the restatement on every case's moments -> T -> criteria
 chain, the Horn solve against a float64 SVD, the order-independence of the sums, the recovered
-motion, the ABI and the C++ shim."""
+motion, the ABI and the C++ shim; the fast exact reference (icp_ref.correspondences_fast) against
+the brute force, and what each generated input of the device tests (scatter, the scale ladder, the
+degenerate clouds, the contract cases) is for."""
 import ctypes as C
 import json
 import os
@@ -128,6 +130,136 @@ def test_horn_against_svd(results):
         assert abs(np.linalg.det(Rm) - 1.0) < 1e-12 and np.allclose(Rm @ Rm.T, np.eye(3), atol=1e-12)
 
 
+# ---- the fast reference and the generated inputs ------------------------------------------------------
+@pytest.fixture(scope="module")
+def scatter():
+    c = R.scatter_case()
+    c["nn"], c["d2"] = R.correspondences(c["src"], c["tgt"])
+    return c
+
+
+def same_pairs(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1]))
+
+
+def test_fast_reference_equals_brute_force(cases, scatter):
+    """correspondences_fast against correspondences, bit for bit in nn and d2, on every golden case,
+    on the scatter case (with and without a max_dist) and on the ties lattice, which has to come out
+    through the fallback"""
+    for name, c in cases.items():
+        W = c["src"] if "indices" not in c else c["src"][c["indices"]]
+        md = c.get("max_dist", R.DBL_MAX ** 0.5)
+        info = {}
+        assert same_pairs(R.correspondences_fast(W, c["tgt"], md, info=info),
+                          R.correspondences(W, c["tgt"], md)), name
+        assert info["queries"] == int(np.isfinite(W).all(axis=1).sum())
+        if name == "ties":  # 8 equidistant corners: the 4th candidate is no farther than the 1st
+            assert info["uncertified"] == info["queries"] == 125
+        else:
+            assert info["uncertified"] <= 0.01 * info["queries"], name
+    md = float(np.median(scatter["d2"][scatter["nn"] >= 0].astype(np.float64))) ** 0.5
+    for m in (R.DBL_MAX ** 0.5, md):
+        info = {}
+        assert same_pairs(R.correspondences_fast(scatter["src"], scatter["tgt"], m, info=info),
+                          R.correspondences(scatter["src"], scatter["tgt"], m))
+        assert info["uncertified"] <= 0.01 * info["queries"]
+    # fewer target points than candidates, and subnormal d2 (below the certificate's floor)
+    few = cases["shadow"]["tgt"][:3]
+    assert same_pairs(R.correspondences_fast(cases["shadow"]["src"], few),
+                      R.correspondences(cases["shadow"]["src"], few))
+    tiny = R.scaled_case(cases["shadow_moved"], -60)
+    info = {}
+    assert same_pairs(R.correspondences_fast(tiny["src"], tiny["tgt"], info=info),
+                      R.correspondences(tiny["src"], tiny["tgt"]))
+    assert info["uncertified"] == info["queries"]
+    # the loop on the fast function: the same bits as the loop on the brute force
+    a = R.run_case(cases["shadow_maxdist"], fast=True)
+    b = R.run_case(cases["shadow_maxdist"])
+    assert np.array_equal(bits(a["final"]), bits(b["final"])) and a["fitness"] == b["fitness"]
+    assert np.array_equal(bits(a["aligned"]), bits(b["aligned"]))
+
+
+def test_scatter_is_what_it_is_for(scatter):
+    src, nn, d2 = scatter["src"], scatter["nn"], scatter["d2"]
+    assert len(src) % 256 != 0 and 2900 <= len(src) <= 3100 and 2900 <= len(scatter["tgt"]) <= 3100
+    fin = np.isfinite(src).all(axis=1)
+    assert 0 < (~fin).sum() <= 16 and np.array_equal(nn >= 0, fin)
+    # every workgroup of 256 holds entries of every part of the ladder (and so of every level)
+    d = np.sqrt(d2.astype(np.float64)) / scatter["spacing"]
+    for a in range(0, len(src), 256):
+        blk = d[a:a + 256][fin[a:a + 256]]
+        assert (blk < 2).any() and ((blk > 8) & (blk < 64)).any() and (blk > 256).any(), a
+    md = float(np.median(d2[fin].astype(np.float64))) ** 0.5
+    kn, kd = R.correspondences(src, scatter["tgt"], md)
+    kept = kd[kn >= 0].astype(np.float64)
+    assert 0.2 * len(src) <= len(kept) <= 0.8 * len(src)
+    lo, hi = np.percentile(kept, 10), np.percentile(kept, 90)
+    print("scatter: kept", len(kept), "of", len(src), "d2 p90 / p10 = 2^%.2f" % np.log2(hi / lo))
+    assert hi >= lo * 2.0 ** 16
+
+
+def test_transformation_epsilon_ends_by_transform(cases):
+    c = cases["shadow_moved"]
+    r = R.align(c["src"], c["tgt"], transformation_epsilon=1e-5)
+    assert (r["state"], r["iterations"], r["converged"]) == (R.TRANSFORM, 5, 1)
+    assert R.align(c["src"], c["tgt"])["iterations"] == 7
+
+
+def test_fitness_range(cases, results):
+    """getFitnessScore keeps d2 <= max_range: a NaN or a negative range keeps nothing (DBL_MAX), the
+    median of the final pass's d2 keeps between 20 % and 80 %"""
+    c, r = cases["shadow_moved"], results["shadow_moved"]
+    W, tgt = r["aligned"], c["tgt"]
+    assert R.fitness_score(W, tgt, float("nan")) == R.DBL_MAX
+    assert R.fitness_score(W, tgt, -1.0) == R.DBL_MAX
+    assert R.fitness_score(W, tgt, R.DBL_MAX) == r["fitness"] < 1e-3
+    nn, d2 = R.correspondences(W, tgt)
+    mr = float(np.median(d2.astype(np.float64)))
+    k = d2.astype(np.float64) <= mr
+    assert 0.2 * len(W) <= k.sum() <= 0.8 * len(W)
+    f = R.fitness_score(W, tgt, mr)
+    assert 0.0 < f < r["fitness"]
+    assert f == R.align(c["src"], tgt, fitness_max_range=mr)["fitness"]
+    # the sum as the mse's: exact integers of the kept d2 at their own exponent
+    e2 = R.qexp(d2[k].max())
+    assert f == float(int(R.quantise(d2[k], e2).sum())) / float(int(k.sum())) * 2.0 ** (e2 - 48)
+
+
+def test_scale_ladder_is_what_it_is_for(cases):
+    base = cases["shadow_moved"]
+    tiny = float(np.finfo(f32).tiny)
+    for k in R.SCALE_RUNGS:
+        c = R.scaled_case(base, k)
+        assert np.array_equal(np.ldexp(c["src"].astype(np.float64), -k), base["src"])  # exact
+        nn, d2 = R.correspondences(c["src"], c["tgt"])
+        assert (nn >= 0).all() and np.isfinite(d2).all()
+        if k == -70:
+            assert (d2 == 0).all()
+        if k == -60:
+            assert ((d2 > 0) & (d2 < tiny)).any()
+        if k == 60:
+            assert d2.max() < np.finfo(f32).max and d2.min() > 0
+    # upward the runs are the unscaled run scaled exactly
+    r0, r60 = R.align(base["src"], base["tgt"], max_iterations=4), \
+        R.align(**R.scaled_case(base, 60), max_iterations=4)
+    assert np.array_equal(bits(np.ldexp(r0["aligned"], 60)), bits(r60["aligned"]))
+    assert np.array_equal(bits(r0["final"][:3, :3]), bits(r60["final"][:3, :3]))
+
+
+def test_degenerate_clouds_are_degenerate():
+    d = R.degenerate_cases()
+    p, ln = d["plane"], d["line"]
+    assert (bits(p["tgt"][:, 2]) == bits(f32(0.25))).all() and (bits(p["src"][:, 2]) == bits(f32(0.26))).all()
+    assert (bits(ln["tgt"][:, 1:]) == 0).all() and np.abs(ln["src"][:, 1:]).max() > 0
+    for c in (p, ln):
+        assert 200 <= len(c["src"]) <= 500 and 200 <= len(c["tgt"]) <= 500
+    # the plane pair: a rank-deficient M (every pair has the same z on each side)
+    r = R.align(p["src"], p["tgt"], max_iterations=1, keep_pairs=True)
+    (w, t, d2), h = r["pairs"][0], r["history"][0]
+    M = np.array(R.rounded_moments(R.moments(w, t, d2, h["e"], h["e2"])))
+    assert (M[2] == 0).all() and (M[:, 2] == 0).all()
+
+
 # ---- the model header --------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model_exe(tmp_path_factory):
@@ -225,7 +357,7 @@ def test_icp_struct_layouts_match_the_header():
     assert L.dlg_abi_struct_size(14) == C.sizeof(_lib.IcpStats) == 80
     assert L.dlg_abi_struct_size(15) == C.sizeof(_lib.IcpIteration) == 88
     assert L.dlg_abi_struct_size(16) == -1 and L.dlg_abi_version() == 5
-    assert _lib.DLG_OPT_ICP_REVERSED == 26
+    assert _lib.DLG_OPT_ICP_REVERSED == 26 and _lib.DLG_OPT_ICP_MAX_BLOCKS == 27
     for s in ("dlg_icp_align", "dlg_icp_correspondences", "dlg_icp_params_default"):
         assert s in _lib.SYMBOLS and hasattr(L, s)
     p = _lib.IcpParams()
