@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "grid_model.hpp"
 #include "normals.hpp"
 
 namespace dlg {
@@ -23,10 +24,7 @@ __device__ __forceinline__ uint32_t hash_key(uint32_t k) {
   return k;
 }
 
-__device__ __forceinline__ int cell_of(float v, float lo, float inv_cell, int g) {
-  int c = (int)floorf((v - lo) * inv_cell);
-  return c < 0 ? 0 : (c >= g ? g - 1 : c);
-}
+// (cell_of, the map from a coordinate to its cell: grid_model.hpp)
 
 __device__ __forceinline__ uint32_t cell_key(const GridDesc& G, int x, int y, int z) {
   return (uint32_t)((z * G.g[1] + y) * G.g[0] + x);

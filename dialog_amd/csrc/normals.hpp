@@ -7,19 +7,9 @@
 #include <cstddef>
 #include <cstdint>
 
-namespace dlg {
+#include "grid_model.hpp"  // GridDesc
 
-// Uniform grid over the cloud's bounding box; cell edge >= the search radius so a radius query
-// touches at most the 27 cells around its own.  Cell key = (cz * gy + cy) * gx + cx < ncells
-// <= 2^30; key ncells marks a non-finite point (sorted last, never inserted).
-struct GridDesc {
-  float lo[3];
-  float cell;
-  float inv_cell;
-  int g[3];
-  uint32_t ncells;
-  int key_bits;
-};
+namespace dlg {
 
 // Device buffers of one grid (owned by the caller).  Sorted order: position t holds point
 // idx_out[t] with coordinates (sx, sy, sz)[t]; the open-addressing cell table maps an occupied

@@ -54,33 +54,6 @@ BBox upload_points(dlg_ctx* c, const dlg_points* pts) {
   return bbox_of(c, w.x.p, w.y.p, w.z.p, n);
 }
 
-// grid with cell edge `cell` (grown until the key space fits 2^30 cells)
-GridDesc make_grid(const BBox& b, double cell) {
-  GridDesc G;
-  for (;;) {
-    double tot = 1.0;
-    for (int k = 0; k < 3; ++k) {
-      const double ext = b.any ? (double)b.hi[k] - (double)b.lo[k] : 0.0;
-      const double gk = std::floor(ext / cell) + 1.0;
-      G.g[k] = (int)std::min(gk, 1e9);
-      tot *= gk;
-    }
-    if (tot <= (double)(1u << 30)) break;
-    cell *= 1.25;
-  }
-  for (int k = 0; k < 3; ++k) G.lo[k] = b.any ? b.lo[k] : 0.0f;
-  // cell_of() computes floor((v - lo) * inv_cell) in float; shrinking inv_cell by 1e-3 keeps the
-  // effective cell edge >= `cell` despite the rounding of (v - lo) and of the product (<= 1024
-  // cells per axis at float precision: ~1e-4 cell), so points within r stay in adjacent cells
-  G.inv_cell = (float)((1.0 / cell) * (1.0 - 1e-3));
-  G.cell = (float)(cell * (1.0 - 1e-6));  // guaranteed coverage radius of the 27 cells
-  G.ncells = (uint32_t)((uint64_t)G.g[0] * G.g[1] * G.g[2]);
-  int bits = 1;
-  while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)G.ncells) ++bits;
-  G.key_bits = bits;
-  return G;
-}
-
 // builds grid level `lv` over (X, Y, Z) (default nw.x/y/z); returns the number of occupied cells
 // (and the point-weighted mean occupancy sum(occ^2) / n in *pw_occ)
 // (clouds from this size gather their sorted coordinates from packed records)

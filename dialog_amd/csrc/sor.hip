@@ -113,14 +113,11 @@ __global__ __launch_bounds__(kBS) void k_sor_knn(KnnLevels L, int l, const int32
   const int cx = cell_of(qx, G.lo[0], G.inv_cell, G.g[0]);
   const int cy = cell_of(qy, G.lo[1], G.inv_cell, G.g[1]);
   const int cz = cell_of(qz, G.lo[2], G.inv_cell, G.g[2]);
-  const float w = 1.0f / G.inv_cell;
-  const float fx = (qx - G.lo[0]) * G.inv_cell - (float)cx;
-  const float fy = (qy - G.lo[1]) * G.inv_cell - (float)cy;
-  const float fz = (qz - G.lo[2]) * G.inv_cell - (float)cz;
-  auto side = [&](float f, int d) {
-    const float v = d < 0 ? f : d > 0 ? 1.0f - f : 0.0f;
-    return v > 1e-4f ? (v - 1e-4f) * w : 0.0f;
-  };
+  const float w = knn_width(G.inv_cell);
+  const float fx = knn_frac(qx, G.lo[0], G.inv_cell, cx);
+  const float fy = knn_frac(qy, G.lo[1], G.inv_cell, cy);
+  const float fz = knn_frac(qz, G.lo[2], G.inv_cell, cz);
+  auto side = [&](float f, int d) { return knn_side(f, d, w, G.slack); };
   const float bx0 = side(fx, -1), bx1 = side(fx, 1), by0 = side(fy, -1), by1 = side(fy, 1);
   const float bz0 = side(fz, -1), bz1 = side(fz, 1);
   constexpr uint64_t kOrd[3] = {0x904416665151515ull, 0x1a9864a9261058ull, 0x2a2a20a8220ull};
@@ -134,7 +131,7 @@ __global__ __launch_bounds__(kBS) void k_sor_knn(KnnLevels L, int l, const int32
     const float ex = dx < 0 ? bx0 : dx > 0 ? bx1 : 0.0f;
     const float ey = dy < 0 ? by0 : dy > 0 ? by1 : 0.0f;
     const float ez = dz < 0 ? bz0 : dz > 0 ? bz1 : 0.0f;
-    const float md = (ex * ex + ey * ey + ez * ez) * (1.0f - 1e-5f);
+    const float md = knn_bound(ex, ey, ez);
     if (md >= lim || (kth != 0xffffffffu && md > __uint_as_float(kth))) continue;
     const int2 rg = cell_range(L.tkeys[l], L.trange[l], L.tmask[l], cell_key(G, x, y, z));
     const int a = __builtin_amdgcn_readfirstlane(rg.x), b = __builtin_amdgcn_readfirstlane(rg.y);
