@@ -41,7 +41,7 @@ SYMBOLS = [
     "dlg_voxel_grid", "dlg_voxel_grid_cloud",
     "dlg_statistical_outlier_removal", "dlg_statistical_outlier_removal_cloud",
     "dlg_moving_least_squares", "dlg_moving_least_squares_cloud",
-    "dlg_icp_params_default", "dlg_icp_align", "dlg_icp_correspondences",
+    "dlg_icp_params_default", "dlg_icp_align", "dlg_icp_correspondences", "dlg_cull_stats",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -72,6 +72,7 @@ DLG_OPT_VOXEL_LONG_RUN = 24
 DLG_OPT_SOR_LITERAL = 25
 DLG_OPT_ICP_REVERSED = 26
 DLG_OPT_ICP_MAX_BLOCKS = 27
+DLG_OPT_CULL = 28
 DLG_ICP_NOT_CONVERGED = 0
 DLG_ICP_ITERATIONS = 1
 DLG_ICP_TRANSFORM = 2
@@ -84,6 +85,8 @@ DLG_TILE_MFMA = 2
 DLG_SCORE_EXACT = 0
 DLG_SCORE_BF16 = 1
 DLG_SCORE_PRUNED = 2
+DLG_SCORE_BOUND = 3
+DLG_SCORE_CULLED = 4
 
 
 class Points(C.Structure):
@@ -239,6 +242,7 @@ def load():
     L.dlg_ctx_set_option.argtypes = [vp, C.c_int, C.c_int64]
     L.dlg_ctx_get_option.argtypes = [vp, C.c_int, i64p]
     L.dlg_prune_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+    L.dlg_cull_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.dlg_preprocess.argtypes = [vp, C.POINTER(Points), C.c_int, C.c_float, fp, C.c_int64, i32p,
                                  C.c_int64, i64p, fp]
     L.dlg_orient_normals_nn.argtypes = [vp, C.POINTER(Points), fp, C.c_int64, C.POINTER(Points),

@@ -291,6 +291,8 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   c->mw.release();
   c->iw.release();
   c->pstats.release();
+  c->cull_i.release();
+  c->cull_h.release();
   c->sel1_status.release();
   c->sel1_err.release();
   c->sel1_tk.release();
@@ -559,6 +561,7 @@ dlg_status dlg_sac_segment(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params* prm,
   dlg_sac_stats* st = stats ? stats : &local;
   return guarded_group(c, [&] {
     HypShardScope hs(c, hyp_shard_on(c, cl));
+    c->cull_off = false;
     std::memset(coeff_out, 0, 4 * sizeof(float));
     *n_inliers = 0;
     SegOut so = segment_round(c, cl, *prm, false, st, nullptr);
@@ -594,6 +597,7 @@ dlg_status dlg_extract_planes(dlg_ctx* c, dlg_cloud* cl, const dlg_sac_params* p
   auto t0 = std::chrono::steady_clock::now();
   dlg_status s = guarded_group(c, [&] {
     HypShardScope hs(c, hyp_shard_on(c, cl));
+    c->cull_off = false;  // (DLG_OPT_CULL's fallback lasts one call)
     *n_planes = 0;
     if (max_planes > 0) offsets_out[0] = 0;
     int64_t written = 0;
@@ -762,8 +766,11 @@ dlg_status dlg_float_sums(dlg_ctx* c, const float* xyz, int64_t n, const float c
 dlg_status dlg_score_benchmark(dlg_ctx* c, dlg_cloud* cl, int D, int kernel, int reps,
                                double threshold, double* ms_per_launch, int32_t* counts_out) {
   if (!c || !cl || D < 1 || D > kMaxHypPerLaunch || reps < 1 || !ms_per_launch) return DLG_ERR_INVALID;
-  if (kernel != kScoreExact && kernel != kScoreBf16 && kernel != kScorePruned) return DLG_ERR_INVALID;
+  if (kernel != kScoreExact && kernel != kScoreBf16 && kernel != kScorePruned &&
+      kernel != DLG_SCORE_BOUND && kernel != DLG_SCORE_CULLED)
+    return DLG_ERR_INVALID;
   const int variant = kernel;
+  const bool culled = kernel == DLG_SCORE_BOUND || kernel == DLG_SCORE_CULLED;
   return guarded(c, [&] {
     ensure_list_xyz(c, cl);
     const PointsView src = cl->view();
@@ -776,7 +783,7 @@ dlg_status dlg_score_benchmark(dlg_ctx* c, dlg_cloud* cl, int D, int kernel, int
     c->hyps.ensure(kHypScratchBytes / sizeof(HypRec) + 1);
     c->res.ensure(2 * (size_t)kMaxHypPerLaunch + 64);
     const float cthr = thr_ceil(threshold);
-    if (variant == kScorePruned && cl->sp_valid) ensure_sphere_bounds(c, cl);
+    if ((variant == kScorePruned || culled) && cl->sp_valid) ensure_sphere_bounds(c, cl);
     HIPCHK(hipMemcpyAsync(c->pos.p, c->h_pos.p, 12 * (size_t)D, hipMemcpyHostToDevice, c->stream));
     launch_gather_samples(c->pos.p, 3 * D, 0, src, c->samples.p, c->stream);
     const int Dp = (D + 63) / 64 * 64;
@@ -784,9 +791,20 @@ dlg_status dlg_score_benchmark(dlg_ctx* c, dlg_cloud* cl, int D, int kernel, int
                       c->res.p + Dp, c->stream);
     double total = 0.0;
     for (int r = 0; r < reps; ++r) {
-      HIPCHK(hipMemsetAsync(c->res.p, 0, 4 * (size_t)Dp, c->stream));
+      // (DLG_SCORE_CULLED: a hypothesis no pass scores keeps the fill, -1)
+      HIPCHK(hipMemsetAsync(c->res.p, kernel == DLG_SCORE_CULLED ? 0xFF : 0, 4 * (size_t)Dp, c->stream));
       HIPCHK(hipEventRecord(c->ev[0], c->stream));
-      if (variant == kScorePruned) {
+      if (culled) {
+        // the culled round's launches (spatial.hpp) with DLG_OPT_CULL's K, without the pick
+        if (!cl->sp_valid || cl->sp_n <= 0) throw DlgError(DLG_ERR_INVALID, "cloud has no spatial copy");
+        c->lp.ensure((size_t)sp_supers(cl->sp_n) * prune_list_stride(D) + 1);
+        ensure_prune_work(c, sp_supers(cl->sp_n));
+        const int K = cull_k(c->opt.cull);
+        launch_score_culled(spatial_view(cl), c->hyps.p, D, Dp, K, cthr, prune_margin(cthr, cl->amax),
+                            c->res.p, c->lp.p, c->lp_n.p + kPwHeader, c->num_cus, c->stream,
+                            prune_stats_ptr(c), ensure_cull(c), nullptr, nullptr, nullptr,
+                            kernel == DLG_SCORE_BOUND ? kCullBenchBound : kCullBenchCounts);
+      } else if (variant == kScorePruned) {
         if (!cl->sp_valid) throw DlgError(DLG_ERR_INVALID, "cloud has no spatial copy");
         c->lp.ensure((size_t)sp_supers(cl->sp_n) * prune_list_stride(D) + 1);
         ensure_prune_work(c, sp_supers(cl->sp_n));
@@ -853,6 +871,7 @@ const OptRow kOptions[] = {
     OPT(DLG_OPT_SOR_LITERAL, sor_literal, 0, 3, "0..3"),
     OPT_BOOL(DLG_OPT_ICP_REVERSED, icp_reversed),
     OPT(DLG_OPT_ICP_MAX_BLOCKS, icp_max_blocks, 0, 65536, "0..65536"),
+    OPT(DLG_OPT_CULL, cull, 0, kMaxHypPerLaunch, "0..4096"),
 };
 #undef OPT_BOOL
 #undef OPT
@@ -913,6 +932,18 @@ dlg_status dlg_prune_stats(dlg_ctx* c, uint64_t out[8], int reset) {
     if (!c->opt.prune_stats) return;
     HIPCHK(hipMemcpyAsync(out, c->pstats.p, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (reset) HIPCHK(hipMemsetAsync(c->pstats.p, 0, 8 * sizeof(unsigned long long), c->stream));
+    sync(c);
+  });
+}
+
+dlg_status dlg_cull_stats(dlg_ctx* c, uint64_t out[8], int reset) {
+  if (!c || !out) return DLG_ERR_INVALID;
+  return guarded(c, [&] {
+    std::memset(out, 0, kCullStats * sizeof(uint64_t));
+    if (!c->cull_i.p) return;  // (no culled round yet)
+    unsigned long long* st = ensure_cull(c).stats;
+    HIPCHK(hipMemcpyAsync(out, st, kCullStats * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (reset) HIPCHK(hipMemsetAsync(st, 0, kCullStats * sizeof(unsigned long long), c->stream));
     sync(c);
   });
 }

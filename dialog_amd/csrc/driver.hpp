@@ -263,6 +263,9 @@ struct PathOptions {
                             // the last entry to the first (icp.hip)
   int icp_max_blocks = 0;   // DLG_OPT_ICP_MAX_BLOCKS (tests only): n >= 1 caps the workgroups of
                             // every launch of the registration (icp.hip); 0 the default shapes
+  int cull = 1;             // DLG_OPT_CULL: probability-1 rounds score only the hypotheses whose
+                            // tile bound can still win (spatial.hpp): 0 off, 1 = the 64 largest
+                            // bounds first, n >= 2 = the n largest first
 };
 
 struct dlg_ctx {
@@ -315,6 +318,12 @@ struct dlg_ctx {
   DevBuf<uint16_t> lp;     // pruned scoring: per super-tile lists of near planes
   DevBuf<int32_t> lp_n;
   DevBuf<unsigned long long> pstats;  // pruned-kernel work counters (DLG_OPT_PRUNE_STATS)
+  // culled scoring (DLG_OPT_CULL; spatial.hpp CullBufs): the bound pass's tile counts, the two
+  // compacted candidate sets and the counters of dlg_cull_stats; zeroed when allocated
+  DevBuf<int32_t> cull_i;
+  DevBuf<HypRec> cull_h;
+  bool cull_off = false;  // a round of this call scored more than D / 16 hypotheses: the rest
+                          // of the call scores unculled
   PinBuf<float4> h_small;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   std::vector<int32_t> h_inl;

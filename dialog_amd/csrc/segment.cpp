@@ -298,6 +298,15 @@ unsigned long long* prune_stats_ptr(dlg_ctx* c) {
   return c->opt.prune_stats ? c->pstats.p : nullptr;
 }
 
+CullBufs ensure_cull(dlg_ctx* c) {
+  if (!c->cull_i.p) {
+    c->cull_i.ensure(cull_int_words());
+    c->cull_h.ensure(2 * (size_t)kMaxHypPerLaunch);
+    HIPCHK(hipMemsetAsync(c->cull_i.p, 0, sizeof(int32_t) * c->cull_i.cap, c->stream));
+  }
+  return cull_bufs(c->cull_i.p, c->cull_h.p);
+}
+
 namespace {
 // a count as a buffer size: never 0
 size_t at_least_1(int64_t n) { return (size_t)std::max<int64_t>(n, 1); }
@@ -417,7 +426,7 @@ void ensure_zeroed(dlg_ctx* c, DevBuf<unsigned>& w) {
 // compact) before anything is enqueued; the phases only read it
 struct RoundPlan {
   bool np, pcl_refit, pcl_dev, pruned, pruned_np, pruned_any, lean, spec, sp_compact, fuse_pick,
-      ext_ev, fused_pub;
+      ext_ev, fused_pub, cull;
   int cap_h;  // draws per scoring launch
   float np_lim = INFINITY, pmargin, cthr;
   ModelTest mt;
@@ -473,6 +482,10 @@ RoundPlan make_plan(const dlg_ctx* c, const dlg_cloud* cl, const dlg_sac_params&
   // the speculative pick: fused into the pruned scoring's last workgroup on one rank (at N > 1
   // it needs the allreduced counts: its own launch after the collective)
   p.fuse_pick = p.spec && p.pruned_any && one && !c->hcomm;
+  // culled scoring (DLG_OPT_CULL; spatial.hpp): the speculative batch of a plane-model round on
+  // one rank, exact tile scorer; off for the rest of a call once a round scored most of its batch
+  p.cull = p.fuse_pick && p.pruned && o.cull != 0 && o.tile_scorer == DLG_TILE_EXACT &&
+           !c->cull_off && cl->sp_n > 0;
   // the pruned scorer records its timing events on its own dispatches (no marker packets)
   p.ext_ev = c->profiling && p.pruned_any;
   p.fused_pub = p.lean && one;  // (the Morton select's last tile publishes the round)
@@ -543,6 +556,7 @@ struct SegmentRound {
   int launches = 0;
   int spec_D = 0, spec_Dp = 0;  // the speculative batch, its counts not yet replayed
   bool spec_pending = false;
+  bool spec_culled = false;  // ... scored culled: res[Dp + D] = the hypotheses scored exactly
   double t_ref0 = 0.0;
   SegOut out;
 
@@ -686,11 +700,21 @@ struct SegmentRound {
       ensure_prune_work(c, sp_supers(cl->sp_n));
       if (P.pruned_np) c->np_cn.ensure(kMaxHypPerLaunch);
       const PrunedNp npp{cl->sp_soa().nrm.p, prm.normal_distance_weight, prm.threshold, c->np_cn.p};
-      launch_score_pruned(spatial_view(cl), hyps_s, Ds, P.cthr, P.pmargin, cl->amax, counts_s,
-                          c->lp.p, c->lp_n.p + kPwHeader, c->num_cus, c->stream, prune_stats_ptr(c),
-                          P.pruned_np ? &npp : nullptr, fuse_pick ? &pk : nullptr,
-                          P.ext_ev ? c->ev[0] : nullptr, P.ext_ev ? c->ev[1] : nullptr,
-                          c->opt.tile_scorer);
+      // (the speculative batch of one rank: Ds == D, the whole of res)
+      spec_culled = fuse_pick && P.cull && Ds > 0;
+      if (spec_culled) {
+        const int K = cull_k(c->opt.cull);
+        launch_score_culled(spatial_view(cl), hyps_s, Ds, Dp, K, P.cthr, P.pmargin, counts_s, c->lp.p,
+                            c->lp_n.p + kPwHeader, c->num_cus, c->stream, prune_stats_ptr(c), ensure_cull(c), &pk,
+                            P.ext_ev ? c->ev[0] : nullptr,
+                            P.ext_ev ? c->ev[1] : nullptr, kCullRound);
+      } else {
+        launch_score_pruned(spatial_view(cl), hyps_s, Ds, P.cthr, P.pmargin, cl->amax, counts_s,
+                            c->lp.p, c->lp_n.p + kPwHeader, c->num_cus, c->stream, prune_stats_ptr(c),
+                            P.pruned_np ? &npp : nullptr, fuse_pick ? &pk : nullptr,
+                            P.ext_ev ? c->ev[0] : nullptr, P.ext_ev ? c->ev[1] : nullptr,
+                            c->opt.tile_scorer);
+      }
     } else if (P.np) {
       if (Ds > 0) launch_score_np(src, hyps_s, Ds, P.mt, counts_s, c->num_cus, c->stream);
     } else if (Ds > 0) {
@@ -700,7 +724,7 @@ struct SegmentRound {
     if (c->profiling && !P.ext_ev) HIPCHK(hipEventRecord(c->ev[1], c->stream));
     if (W > 1) c->comm->allreduce_sum(c->res.p, D, DType::I32, c->stream);
     if (c->hcomm) c->hcomm->allreduce_sum(c->res.p, D, DType::I32, c->stream);
-    c->h_res.ensure((size_t)Dp + D);
+    c->h_res.ensure((size_t)Dp + D + 1);
     ++launches;
     st->tests_scored += (int64_t)D * N;
   }
@@ -751,6 +775,9 @@ struct SegmentRound {
       HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev_score_end));
       st->score_ms += ms;
     }
+    // a culled round that scored more than D / kCullFallbackDiv: the bound does not separate on this
+    // cloud, the rest of the call scores unculled (the bound pass is then paid once)
+    if (spec_culled && cull_falls_back(c->h_res.p[spec_Dp + spec_D], spec_D)) c->cull_off = true;
     const int best_d = ctl.consume(c->h_res.p, c->h_res.p + spec_Dp, spec_D);
     if (ctl.done() && best_d == c->h_pick.p[0] && c->h_pick.p[1] == 1) return true;
     ++c->spec_misses;
@@ -1009,7 +1036,7 @@ struct SegmentRound {
   // (totals[2..3] still hold the previous compaction's Morton-copy totals: checked below)
   PubArgs make_pub_args() {
     const bool with_counts = spec_pending;
-    const int nres = with_counts ? spec_Dp + spec_D : 0;
+    const int nres = with_counts ? spec_Dp + spec_D + (spec_culled ? 1 : 0) : 0;
     const size_t need = (size_t)kPubRk + (W > 1 ? 2 * (size_t)W : 0) + (size_t)nres;
     if (need > c->pub_cap) {
       if (c->pub) HIPCHK(hipHostFree(c->pub));

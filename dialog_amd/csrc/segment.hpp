@@ -48,6 +48,8 @@ void ensure_sphere_bounds(dlg_ctx* c, dlg_cloud* cl);
 void ensure_list_xyz(dlg_ctx* c, dlg_cloud* cl);
 void ensure_prune_work(dlg_ctx* c, int64_t ns);
 unsigned long long* prune_stats_ptr(dlg_ctx* c);
+// the culled scoring's device scratch (allocated and zeroed on first use)
+CullBufs ensure_cull(dlg_ctx* c);
 float event_ms(dlg_ctx* c, int a, int b);
 
 }  // namespace dlg

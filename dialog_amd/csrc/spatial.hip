@@ -218,7 +218,8 @@ __global__ __launch_bounds__(kPrBS) void k_prune_supers(const float4* __restrict
                                                         uint16_t* __restrict__ lp,
                                                         int32_t* __restrict__ lp_n,
                                                         int32_t* __restrict__ work, int order,
-                                                        float4* __restrict__ cn) {
+                                                        float4* __restrict__ cn,
+                                                        int32_t* __restrict__ zero, int n_zero) {
   __shared__ float4 s_cf[kMaxHypPerLaunch];
   __shared__ uint16_t s_hl[kMaxHypPerLaunch];  // the planes near this hyper's sphere
   __shared__ float4 s_sp[kWave];
@@ -226,6 +227,9 @@ __global__ __launch_bounds__(kPrBS) void k_prune_supers(const float4* __restrict
   __shared__ int s_nh;
   const int t = threadIdx.x, lane = t & (kWave - 1);
   if (blockIdx.x == 0 && t < 8) work[t * kPruneWorkStride] = 0;  // the scorers' item counters
+  // (culled rounds: the first prune zeroes the bound pass's per-plane tile counts)
+  if (zero && blockIdx.x == gridDim.x - 1)
+    for (int j = t; j < n_zero; j += kPrBS) zero[j] = 0;
   if (cn && blockIdx.x == gridDim.x - 1)  // (NORMAL_PLANE: Eigen's normalized() of each plane)
     for (int j = t; j < D; j += kPrBS) {
       const HypRec h = hyps[j];
@@ -1224,6 +1228,364 @@ __global__ __launch_bounds__(BS) void k_score_tiles_ex(
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Culled scoring (spatial.hpp): the bound pass and the one-workgroup kernels between the exact
+// passes.  Every dependency is a launch boundary on one stream: no kernel here waits for another
+// workgroup.
+//
+// k_bound_tiles: nt[j] += the tiles whose sphere test plane j passes -- the scorer's own test
+// (sphere_near_lim over the super-tile's list), without points or ring.  One wave per super-tile:
+// lane = list entry (four per lane per step), the super-tile's <= 16 tile spheres with their
+// limits in registers (staged through the wave's LDS row; read from LDS inside the test loop the
+// pass took 59 us at C3 instead of 25), one LDS add per (entry, super-tile), the counters
+// flushed once per workgroup.  Wave w of
+// workgroup b takes super-tiles b + gridDim.x (w + 16 k): with gridDim.x a multiple of 8 they are
+// those of XCD b & 7, as in the scorer.
+constexpr int kBtBS = 1024;
+__global__ __launch_bounds__(kBtBS) void k_bound_tiles(const float4* __restrict__ tiles,
+                                                       int ntiles, const uint16_t* __restrict__ lp,
+                                                       int ls, const int32_t* __restrict__ lp_n,
+                                                       int nsup, const HypRec* __restrict__ hyps,
+                                                       int D, float margin,
+                                                       int32_t* __restrict__ nt) {
+  __shared__ float4 s_cf[kMaxHypPerLaunch];
+  __shared__ int32_t s_nt[kMaxHypPerLaunch];
+  __shared__ float4 s_tb[kBtBS / kWave][kSuperTiles];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  for (int j = threadIdx.x; j < D; j += kBtBS) {
+    const HypRec h = hyps[j];
+    s_cf[j] = make_float4(h.a, h.b, h.c, h.d);
+    s_nt[j] = 0;
+  }
+  __syncthreads();
+  float4* tb = s_tb[wv];
+  for (int64_t s = (int64_t)blockIdx.x + (int64_t)gridDim.x * wv; s < nsup;
+       s += (int64_t)gridDim.x * (kBtBS / kWave)) {
+    const int nlp = __builtin_amdgcn_readfirstlane(lp_n[s]);
+    if (nlp == 0) continue;
+    const int t0 = (int)s * kSuperTiles, nts = min(kSuperTiles, ntiles - t0);
+    __builtin_amdgcn_wave_barrier();  // (the previous super-tile's row is no longer read)
+    if (lane < kSuperTiles) {
+      // (a tile past the end: a NaN sphere, never near)
+      float4 sp = make_float4(__builtin_nanf(""), 0.f, 0.f, 0.f);
+      if (lane < nts) {
+        sp = tiles[t0 + lane];
+        sp.w = prune_lim(margin, sp.w);
+      }
+      tb[lane] = sp;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float4 T[kSuperTiles];  // the super-tile's spheres in registers: no LDS read per test
+#pragma unroll
+    for (int t = 0; t < kSuperTiles; ++t) T[t] = tb[t];
+    // two list words (four entries) per lane per step, loaded before any is tested
+    const uint32_t* lw = reinterpret_cast<const uint32_t*>(lp + s * ls);
+    const int nw = (nlp + 1) >> 1;
+    for (int wb = 0; wb < nw; wb += 2 * kWave) {
+      uint32_t w[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int wi = wb + q * kWave + lane;
+        w[q] = wi < nw ? lw[wi] : 0u;
+      }
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int e = 2 * (wb + q * kWave + lane);
+#pragma unroll
+        for (int hlf = 0; hlf < 2; ++hlf) {
+          if (e + hlf < nlp) {
+            const int j = (int)((w[q] >> (16 * hlf)) & 0xFFFFu);
+            const float4 cf = s_cf[j];
+            int near = 0;
+#pragma unroll
+            for (int t = 0; t < kSuperTiles; ++t) near += sphere_near_lim(cf, T[t], T[t].w) ? 1 : 0;
+            if (near) atomicAdd(&s_nt[j], near);
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < D; j += kBtBS)
+    if (s_nt[j]) atomicAdd(&nt[j], s_nt[j]);
+}
+
+// k_score_supers: the exact counts of a culled round's candidate set (a few dozen planes, their
+// number known only on the device).  k_score_tiles_ex is built for hundreds of near planes per
+// tile: with 64 planes its passes run nearly empty and each 2-tile item waits out its own chain of
+// dependent loads (claim, list length, list, spheres) -- 165 us at C3 behind a 32 us list build.
+// Here one wave takes a super-tile: its 512 points in registers (8 per lane, NaN past n), the
+// planes tested 64 at a time against the super-tile's sphere with the scorer's own test
+// (sphere_near_lim: a plane it rules out has no PCL inlier in the super-tile), and each near plane
+// evaluated on all 512 points with PCL's arithmetic (pcl_dot, fabsf(d) < cthr as the scorers),
+// lanes as points, the verdicts counted by ballots.  No lists, no tile test: a (tile, plane) pair
+// the tile sphere would rule out has no inlier, so evaluating it adds nothing to the count.
+constexpr int kSsBS = 1024;
+constexpr int kSsPer = kSuperP / kWave;  // points per lane
+__global__ __launch_bounds__(kSsBS) void k_score_supers(
+    const float* __restrict__ X, const float* __restrict__ Y, const float* __restrict__ Z, int n,
+    const float4* __restrict__ supers, int nsup, const HypRec* __restrict__ hyps,
+    const int32_t* __restrict__ D_dev, float cthr, float margin, int32_t* __restrict__ counts,
+    unsigned long long* __restrict__ stats) {
+  __shared__ float4 s_cf[kMaxHypPerLaunch];
+  __shared__ int32_t s_cnt[kMaxHypPerLaunch];
+  __shared__ unsigned long long s_st[3];
+  const int D = *D_dev;
+  if (D == 0) return;
+  if (threadIdx.x < 3) s_st[threadIdx.x] = 0;
+  // (stats, dlg_prune_stats: planes tested against super-tile spheres as [1] list entries, tiles
+  // visited [2], (tile, plane) pairs evaluated [4] -- all the tiles of a near super-tile -- and
+  // their 128-pair passes [3])
+  unsigned long long st_e = 0, st_t = 0, st_p = 0;
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  for (int j = threadIdx.x; j < D; j += kSsBS) {
+    const HypRec h = hyps[j];
+    s_cf[j] = make_float4(h.a, h.b, h.c, h.d);
+    s_cnt[j] = 0;
+  }
+  __syncthreads();
+  for (int64_t s = (int64_t)blockIdx.x + (int64_t)gridDim.x * wv; s < nsup;
+       s += (int64_t)gridDim.x * (kSsBS / kWave)) {
+    float4 sp = supers[s];
+    sp.w = prune_lim(margin, sp.w);
+    float x[kSsPer], y[kSsPer], z[kSsPer];
+#pragma unroll
+    for (int k = 0; k < kSsPer; ++k) {
+      const int64_t p = s * kSuperP + k * kWave + lane;
+      x[k] = y[k] = z[k] = __builtin_nanf("");  // (never an inlier: PCL's NaN < thr is false)
+      if (p < n) { x[k] = X[p]; y[k] = Y[p]; z[k] = Z[p]; }
+    }
+    const int nts = (int)min<int64_t>(kSuperTiles, ((int64_t)n - s * kSuperP + kTileP - 1) / kTileP);
+    st_e += (unsigned long long)D;
+    st_t += (unsigned long long)nts;
+    for (int j0 = 0; j0 < D; j0 += kWave) {
+      const int j = j0 + lane;
+      uint64_t near = ballot(j < D && sphere_near_lim(s_cf[min(j, D - 1)], sp, sp.w));
+      st_p += (unsigned long long)(nts * (int)__popcll(near));
+      while (near) {  // (uniform)
+        const int jj = j0 + (int)__builtin_ctzll(near);
+        near &= near - 1;
+        const float4 c = s_cf[jj];
+        int cnt = 0;
+#pragma unroll
+        for (int k = 0; k < kSsPer; ++k)
+          cnt += (int)__popcll(ballot(fabsf(pcl_dot(c.x, c.y, c.z, c.w, x[k], y[k], z[k])) < cthr));
+        if (lane == 0 && cnt) atomicAdd(&s_cnt[jj], cnt);
+      }
+    }
+  }
+  if (stats && lane == 0) {
+    atomicAdd(&s_st[0], st_e);
+    atomicAdd(&s_st[1], st_t);
+    atomicAdd(&s_st[2], st_p);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < D; j += kSsBS)
+    if (s_cnt[j]) atomicAdd(&counts[j], s_cnt[j]);
+  if (stats && threadIdx.x == 0) {
+    atomicAdd(&stats[0], 1ull);
+    atomicAdd(&stats[1], s_st[0]);
+    atomicAdd(&stats[2], s_st[1]);
+    atomicAdd(&stats[3], (s_st[2] + 127ull) / 128ull);
+    atomicAdd(&stats[4], s_st[2]);
+  }
+}
+
+constexpr int kCullBS = 1024;
+constexpr int kCullPer = kMaxHypPerLaunch / kCullBS;  // hypotheses per thread (consecutive)
+static_assert(kMaxHypPerLaunch % kCullBS == 0 && kMaxHypPerLaunch <= 4096, "12 index bits in the key");
+
+// the thread's first position when every thread appends c entries in thread order; *total = all
+__device__ __forceinline__ int cull_block_excl(int c, int* s_w, int* total) {
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  int incl = c;
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const int v = __shfl_up(incl, o);
+    if (lane >= o) incl += v;
+  }
+  if (lane == kWave - 1) s_w[w] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int q = 0; q < kCullBS / kWave; ++q) {
+    base += q < w ? s_w[q] : 0;
+    tot += s_w[q];
+  }
+  __syncthreads();
+  *total = tot;
+  return base + incl - c;
+}
+
+// workgroup count of a predicate over the thread's kCullPer entries, by ballots (scalar adds): one
+// barrier per call, s_w2 alternating by `par` (the rows are reused two calls later)
+__device__ __forceinline__ int cull_block_count(const bool (&p)[kCullPer], int (*s_w2)[kCullBS / kWave],
+                                                int par) {
+  int c = 0;
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) c += (int)__popcll(ballot(p[i]));
+  if ((threadIdx.x & (kWave - 1)) == 0) s_w2[par][threadIdx.x / kWave] = c;
+  __syncthreads();
+  int tot = 0;
+#pragma unroll
+  for (int q = 0; q < kCullBS / kWave; ++q) tot += s_w2[par][q];
+  return tot;
+}
+
+// Set A: the K good hypotheses with the largest nt, ties to the lower index; all of them when
+// fewer than K are good.  Key of a good hypothesis h = (nt_h + 1) << 12 | (4095 - h) (distinct,
+// > 0; a bad draw's key is 0); the K-th largest key is found digit by digit (the largest T with
+// #{key >= T} >= K: exactly K keys reach it), from the top bit a key can have (nt <= ntiles).
+// Writes A compacted in index order (HypRecs, batch indices, zeroed counts), the membership
+// marks, n_a and the number of good hypotheses.
+__global__ __launch_bounds__(kCullBS) void k_cull_pick_a(const HypRec* __restrict__ hyps,
+                                                         const int32_t* __restrict__ good, int D,
+                                                         int K, int ntiles, CullBufs cb) {
+  __shared__ int s_w[kCullBS / kWave];
+  __shared__ int s_w2[2][kCullBS / kWave];
+  __shared__ int s_w3[2][3][kCullBS / kWave];  // (alternating rows: one barrier per step)
+  const int h0 = threadIdx.x * kCullPer;
+  unsigned long long key[kCullPer];
+  bool p[kCullPer];
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) {
+    const int h = h0 + i;
+    key[i] = 0ull;
+    if (h < D && good[h] != 0)
+      key[i] = ((unsigned long long)((uint32_t)cb.nt[h] + 1u) << 12) | (unsigned long long)(4095 - h);
+    p[i] = key[i] != 0ull;
+  }
+  int par = 0;
+  const int n_good = cull_block_count(p, s_w2, par);
+  par ^= 1;
+  unsigned long long T = 1ull;  // (every good hypothesis)
+  if (n_good > K) {
+    T = 0ull;
+    // two key bits per step: the largest digit d of 3, 2, 1 with #{key >= T | d << b} >= K
+    const int top = 12 + 32 - __builtin_clz((uint32_t)ntiles + 1u);  // key < 2^top
+    for (int b = (top - 1) & ~1; b >= 0; b -= 2) {
+      int c[3] = {0, 0, 0};
+#pragma unroll
+      for (int d = 1; d <= 3; ++d) {
+        const unsigned long long cand = T | ((unsigned long long)d << b);
+#pragma unroll
+        for (int i = 0; i < kCullPer; ++i) c[d - 1] += (int)__popcll(ballot(key[i] >= cand));
+      }
+      if ((threadIdx.x & (kWave - 1)) == 0) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) s_w3[par][d][threadIdx.x / kWave] = c[d];
+      }
+      __syncthreads();
+      int tot[3] = {0, 0, 0};
+#pragma unroll
+      for (int q = 0; q < kCullBS / kWave; ++q) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) tot[d] += s_w3[par][d][q];
+      }
+      const int dg = tot[2] >= K ? 3 : tot[1] >= K ? 2 : tot[0] >= K ? 1 : 0;
+      T |= (unsigned long long)dg << b;
+      par ^= 1;
+    }
+  }
+  int c = 0;
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) c += key[i] >= T ? 1 : 0;
+  int n_a;
+  int pos = cull_block_excl(c, s_w, &n_a);
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) {
+    const int h = h0 + i;
+    if (h >= D) continue;
+    const bool in = key[i] >= T;
+    cb.mark[h] = in ? 1 : 0;
+    if (in) {
+      cb.hyp_a[pos] = hyps[h];
+      cb.idx_a[pos] = h;
+      cb.cnt_a[pos] = 0;
+      ++pos;
+    }
+  }
+  if (threadIdx.x == 0) {
+    cb.hdr[0] = n_a;
+    cb.hdr[2] = n_good;
+  }
+}
+
+// Set B: with B_cnt = the largest exact count in A, the good hypotheses outside A whose bound
+// 32 nt_h reaches it (>=: a tie can still win by index).  Writes B compacted in index order, n_b,
+// and A's counts into res.
+__global__ __launch_bounds__(kCullBS) void k_cull_pick_b(const HypRec* __restrict__ hyps,
+                                                         const int32_t* __restrict__ good, int D,
+                                                         int32_t* __restrict__ res, CullBufs cb) {
+  __shared__ int s_w[kCullBS / kWave];
+  __shared__ int s_max;
+  const int n_a = cb.hdr[0];
+  if (threadIdx.x == 0) s_max = 0;
+  __syncthreads();
+  int mx = 0;
+  for (int i = threadIdx.x; i < n_a; i += kCullBS) {
+    const int cnt = cb.cnt_a[i];
+    res[cb.idx_a[i]] = cnt;
+    mx = max(mx, cnt);
+  }
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) mx = max(mx, __shfl_xor(mx, o));
+  if ((threadIdx.x & (kWave - 1)) == 0 && mx > 0) atomicMax(&s_max, mx);
+  __syncthreads();
+  const long long b_cnt = s_max;
+  const int h0 = threadIdx.x * kCullPer;
+  bool in[kCullPer];
+  int c = 0;
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) {
+    const int h = h0 + i;
+    in[i] = h < D && good[h] != 0 && cb.mark[h] == 0 && 32ll * cb.nt[h] >= b_cnt;
+    c += in[i] ? 1 : 0;
+  }
+  int n_b;
+  int pos = cull_block_excl(c, s_w, &n_b);
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) {
+    if (!in[i]) continue;
+    cb.hyp_b[pos] = hyps[h0 + i];
+    cb.idx_b[pos] = h0 + i;
+    cb.cnt_b[pos] = 0;
+    ++pos;
+  }
+  if (threadIdx.x == 0) cb.hdr[1] = n_b;
+}
+
+// The tail: B's counts into res (every culled hypothesis keeps the 0, or the caller's fill, it
+// started with), the counters, then -- in a round -- the number of hypotheses scored behind the
+// good flags (res[Dp + D], published with the counts) and computeModel's pick over the full
+// batch exactly as the unculled path runs it.  The pick reads the counts this workgroup has just
+// stored: device-coherent stores, acknowledged before the barrier, and pick_body's coherent loads.
+__global__ __launch_bounds__(kCullBS) void k_cull_tail(int32_t* __restrict__ res, int D, int Dp,
+                                                       CullBufs cb, PickArgs pick_args) {
+  const int n_a = cb.hdr[0], n_b = cb.hdr[1], n_good = cb.hdr[2];
+  for (int i = threadIdx.x; i < n_b; i += kCullBS)
+    __hip_atomic_store(res + cb.idx_b[i], cb.cnt_b[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!pick_args.out) return;  // (dlg_score_benchmark: no round, no counters, no pick)
+  if (threadIdx.x == 0) {
+    cb.stats[0] += 1ull;
+    cb.stats[1] += (unsigned long long)n_a;
+    cb.stats[2] += (unsigned long long)n_b;
+    cb.stats[3] += (unsigned long long)(n_good - n_a - n_b);
+    cb.stats[4] += n_b > 0 ? 1ull : 0ull;
+    cb.stats[5] += kCullFallbackDiv * (n_a + n_b) > D ? 1ull : 0ull;
+    res[Dp + D] = n_a + n_b;
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+  pick_body<kCullBS, true>(pick_args);
+}
+
+// dlg_score_benchmark's bound id: counts[h] = 32 nt_h
+__global__ void k_cull_bound_out(const int32_t* __restrict__ nt, int D, int32_t* __restrict__ counts) {
+  const int h = blockIdx.x * blockDim.x + threadIdx.x;
+  if (h < D) counts[h] = (int32_t)min(32ll * nt[h], (long long)INT_MAX);
+}
+
 __global__ void k_gather_nrm(const float4* __restrict__ src, const int32_t* __restrict__ order,
                              int64_t n, float4* __restrict__ dst) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1317,30 +1679,28 @@ void launch_curv_range(const float4* nrm, int64_t n, uint32_t* out2, hipStream_t
   hipLaunchKernelGGL(k_curv_range, dim3((unsigned)blocks), dim3(256), 0, s, nrm, n, out2);
 }
 
-void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float cthr, float margin,
-                         const float amax[3], int32_t* counts, uint16_t* lp, int32_t* lp_n,
-                         int num_cus, hipStream_t s, unsigned long long* stats, const PrunedNp* np,
-                         const PickArgs* pick, hipEvent_t ev_start, hipEvent_t ev_stop,
-                         int tile_scorer) {
-  if (D <= 0 || v.n <= 0 || D > kMaxHypPerLaunch) {
-    if (ev_start) (void)hipEventRecord(ev_start, s);
-    if (pick) launch_pick_p1(*pick, s);  // (nothing to score: the pick still runs)
-    if (ev_stop) (void)hipEventRecord(ev_stop, s);
-    return;
-  }
-  const int64_t ns = sp_supers(v.n);
-  const int ls = prune_list_stride(D);
+namespace {
+// the launch shapes of k_prune_supers (hypers of H super-tiles, ga workgroups) and of the tile
+// scorers (g workgroups of kBS threads, each capped at blk_cap items; xcd: the XCD-aware mapping)
+constexpr int kBS = 1024, kChunkTiles = 2;
+struct PrunedShape {
+  int64_t ns;
+  int H;
+  unsigned ga;
+  int64_t g;
+  int blk_cap, xcd;
+};
+PrunedShape pruned_shape(int64_t n, int num_cus) {
+  const int64_t ns = sp_supers(n);
   // hypers of H super-tiles (H <= 32, a power of two), as large as keeps >= 2 workgroups per CU
   int H = 1;
   while (H < 32 && ns / (2 * H) >= 2 * (int64_t)num_cus) H *= 2;
   const unsigned ga = (unsigned)std::max<int64_t>(1, (ns + H - 1) / H);
-  int32_t* work = lp_n - kPwHeader;  // (the buffer's header: spatial.hpp)
   // one 1024-thread workgroup per CU (LDS + VGPRs); its waves claim 2-tile items dynamically,
   // each workgroup capped at blk_cap items (16-bit LDS counters: <= 65535 points per
   // workgroup), and enough workgroups that the caps cover every item
-  constexpr int kBS = 1024, kChunkTiles = 2;
   static_assert(kSuperTiles % kChunkTiles == 0, "an item stays inside one super-tile");
-  const int64_t items = (sp_tiles(v.n) + kChunkTiles - 1) / kChunkTiles;
+  const int64_t items = (sp_tiles(n) + kChunkTiles - 1) / kChunkTiles;
   const int blk_cap = 65535 / (kChunkTiles * kTileP);
   int64_t g = std::max<int64_t>(
       1, std::max<int64_t>(std::min<int64_t>(num_cus, (items + kBS / kWave - 1) / (kBS / kWave)),
@@ -1356,6 +1716,26 @@ void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float 
     g = gx;
     xcd = 1;
   }
+  return PrunedShape{ns, H, ga, g, blk_cap, xcd};
+}
+}  // namespace
+
+void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float cthr, float margin,
+                         const float amax[3], int32_t* counts, uint16_t* lp, int32_t* lp_n,
+                         int num_cus, hipStream_t s, unsigned long long* stats, const PrunedNp* np,
+                         const PickArgs* pick, hipEvent_t ev_start, hipEvent_t ev_stop,
+                         int tile_scorer) {
+  if (D <= 0 || v.n <= 0 || D > kMaxHypPerLaunch) {
+    if (ev_start) (void)hipEventRecord(ev_start, s);
+    if (pick) launch_pick_p1(*pick, s);  // (nothing to score: the pick still runs)
+    if (ev_stop) (void)hipEventRecord(ev_stop, s);
+    return;
+  }
+  const PrunedShape sh = pruned_shape(v.n, num_cus);
+  const int64_t ns = sh.ns, g = sh.g;
+  const int ls = prune_list_stride(D), H = sh.H, blk_cap = sh.blk_cap, xcd = sh.xcd;
+  const unsigned ga = sh.ga;
+  int32_t* work = lp_n - kPwHeader;  // (the buffer's header: spatial.hpp)
   // (NORMAL_PLANE: DLG_TILE_BF16 selects round 4's k_score_tiles_rl<NPM>, lanes as points)
   const bool ex = tile_scorer != kTileScorerBf16;
   // (A/B only: 15 = round 4's claim, XCD round-robin without classes or tail; 16 = classes
@@ -1371,7 +1751,7 @@ void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float 
   // launch gaps around the scoring)
   DLG_LAUNCH_EV(k_prune_supers, dim3(ga), dim3(kPrBS), 0, s, ev_start, nullptr, v.supers,
                         (int)ns, hyps, D, ls, margin, H, lp, lp_n, work, order,
-                        np && ex ? np->cn : nullptr);
+                        np && ex ? np->cn : nullptr, (int32_t*)nullptr, 0);
   if (np && ex) {
     DLG_LAUNCH_EV((k_score_tiles_ex<kBS, 2, false, true>), dim3((unsigned)g), dim3(kBS), 0, s,
                           nullptr, ev_stop, v.x, v.y, v.z, (int)v.n, v.tiles, lp, ls, lp_n, work,
@@ -1413,5 +1793,44 @@ void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float 
                         cthr, margin, amax[0], amax[1], amax[2], counts, stats,
                         np ? np->nrm : nullptr, np ? np->lambda : 0.0, np ? np->thr : 0.0,
                         pick ? *pick : PickArgs{});
+}
+
+// (the caller has ruled out D <= 0 and an empty copy)
+void launch_score_culled(const SpatialView& v, const HypRec* hyps, int D, int Dp, int K, float cthr,
+                         float margin, int32_t* res, uint16_t* lp, int32_t* lp_n, int num_cus,
+                         hipStream_t s, unsigned long long* pstats, const CullBufs& cb,
+                         const PickArgs* pick, hipEvent_t ev_start, hipEvent_t ev_stop,
+                         CullMode mode) {
+  const PrunedShape sh = pruned_shape(v.n, num_cus);
+  const int ls = prune_list_stride(D);
+  int32_t* work = lp_n - kPwHeader;
+  const int32_t* good = res + Dp;
+  const int ntiles = (int)sp_tiles(v.n);
+  // all D planes against the super-tiles (no class order: the bound pass deals super-tiles to
+  // waves by index), then the bound pass
+  DLG_LAUNCH_EV(k_prune_supers, dim3(sh.ga), dim3(kPrBS), 0, s, ev_start, nullptr, v.supers,
+                (int)sh.ns, hyps, D, ls, margin, sh.H, lp, lp_n, work, 0, (float4*)nullptr,
+                cb.nt, D);
+  int64_t gb = std::max<int64_t>(1, std::min<int64_t>(num_cus, (sh.ns + kBtBS / kWave - 1) / (kBtBS / kWave)));
+  if (gb >= 8) gb = (gb + 7) / 8 * 8;
+  const bool bound_only = mode == kCullBenchBound;
+  DLG_LAUNCH_EV(k_bound_tiles, dim3((unsigned)gb), dim3(kBtBS), 0, s, nullptr, nullptr,
+                v.tiles, ntiles, lp, ls, lp_n, (int)sh.ns, hyps, D, margin, cb.nt);
+  if (bound_only) {
+    DLG_LAUNCH_EV(k_cull_bound_out, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, nullptr,
+                  ev_stop, cb.nt, D, res);
+    return;
+  }
+  // (one wave per super-tile, as the bound pass)
+  auto exact_pass = [&](const HypRec* h, const int32_t* n_dev, int32_t* counts) {
+    hipLaunchKernelGGL(k_score_supers, dim3((unsigned)gb), dim3(kSsBS), 0, s, v.x, v.y, v.z,
+                       (int)v.n, v.supers, (int)sh.ns, h, n_dev, cthr, margin, counts, pstats);
+  };
+  hipLaunchKernelGGL(k_cull_pick_a, dim3(1), dim3(kCullBS), 0, s, hyps, good, D, K, ntiles, cb);
+  exact_pass(cb.hyp_a, cb.hdr, cb.cnt_a);
+  hipLaunchKernelGGL(k_cull_pick_b, dim3(1), dim3(kCullBS), 0, s, hyps, good, D, res, cb);
+  exact_pass(cb.hyp_b, cb.hdr + 1, cb.cnt_b);
+  DLG_LAUNCH_EV(k_cull_tail, dim3(1), dim3(kCullBS), 0, s, nullptr, ev_stop, res, D, Dp, cb,
+                mode == kCullRound && pick ? *pick : PickArgs{});
 }
 }  // namespace dlg

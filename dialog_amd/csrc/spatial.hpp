@@ -46,9 +46,13 @@ struct SpatialView {
 __device__ __forceinline__ float prune_lim(float margin, float r) {
   return (margin + r) * (1.0f + 0x1p-20f);
 }
-__device__ __forceinline__ bool sphere_near(float4 cf, float4 sp, float margin) {
+// (lim = prune_lim(margin, r) of the sphere, for callers that test many planes against it)
+__device__ __forceinline__ bool sphere_near_lim(float4 cf, float4 sp, float lim) {
   const float h = __builtin_fmaf(cf.x, sp.x, __builtin_fmaf(cf.y, sp.y, __builtin_fmaf(cf.z, sp.z, cf.w)));
-  return fabsf(h) <= prune_lim(margin, sp.w);
+  return fabsf(h) <= lim;
+}
+__device__ __forceinline__ bool sphere_near(float4 cf, float4 sp, float margin) {
+  return sphere_near_lim(cf, sp, prune_lim(margin, sp.w));
 }
 
 // Curve keys over [-amax, amax] per axis, 10 bits per axis: Hilbert (hilbert, the default) or
@@ -120,6 +124,58 @@ void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float 
                          hipEvent_t ev_start = nullptr,   // timing events of the launch pair
                          hipEvent_t ev_stop = nullptr,
                          int tile_scorer = kTileScorerExact);
+// Culled scoring of one probability-1 batch (plane model, exact tile scorer, one rank): only the
+// hypotheses whose tile bound can still win are scored exactly.  A (tile, plane) pair the
+// tile-sphere test rules out has no PCL inlier, so count_h <= 32 nt_h with nt_h = the tiles whose
+// sphere test h passes (k_bound_tiles, no point tests).  Set A = the K good hypotheses with the
+// largest nt (ties: lower index) is scored first; with B_cnt = A's largest exact count, set B = the
+// good hypotheses outside A with 32 nt_h >= B_cnt is scored next; every other hypothesis has a
+// count strictly below B_cnt and keeps the count 0 it started with.  computeModel's first strict
+// maximum over the good draws is therefore the same draw with the same count.
+// Stream order: k_prune_supers (all D) -> k_bound_tiles -> k_cull_pick_a -> k_score_supers (A)
+// -> k_cull_pick_b -> k_score_supers (B) -> k_cull_tail (counts scattered into res, then the
+// pick).  The exact passes read their plane counts from device memory (hdr[0], hdr[1]); a pass
+// with no plane returns at once.  Every dependency is a launch boundary on the one stream.
+constexpr int kCullDefaultK = 64;
+// DLG_OPT_CULL's value (>= 1) as K
+inline int cull_k(int opt) { return opt <= 1 ? kCullDefaultK : opt; }
+// A round that scores more than D / kCullFallbackDiv hypotheses exactly turns culling off for the
+// rest of the call.  k_score_supers prunes by super-tile only and costs ~9x the tile scorer per
+// plane (C3: 0.51 against 0.056 us), and a culled round spends ~0.36 of the unculled round before
+// any exact test (prune, bound, selection): it pays up to (1 - 0.36) / 9.2 = D / 14 planes
+// (DESIGN.md §7).
+constexpr int kCullFallbackDiv = 16;
+inline bool cull_falls_back(int64_t scored, int64_t D) { return kCullFallbackDiv * scored > D; }
+constexpr int kCullHdrWords = 16;  // [0] n_a, [1] n_b, [2] good hypotheses of the batch
+// dlg_cull_stats' counters: rounds culled, hypotheses scored in pass A, in pass B, good hypotheses
+// culled, rounds with a non-empty pass B, rounds that scored more than D / kCullFallbackDiv
+// (fell back).  Only rounds count: dlg_score_benchmark's ids leave the counters alone
+constexpr int kCullStats = 8;
+struct CullBufs {  // device scratch, every array kMaxHypPerLaunch long
+  int32_t* nt;     // tiles whose sphere test each hypothesis passes (zeroed by the first prune)
+  int32_t* mark;   // 1: the hypothesis is in set A
+  int32_t *idx_a, *cnt_a, *idx_b, *cnt_b;  // compacted sets: batch index and exact count
+  HypRec *hyp_a, *hyp_b;
+  int32_t* hdr;    // [kCullHdrWords]
+  unsigned long long* stats;  // [kCullStats]
+};
+inline size_t cull_int_words() { return 6 * (size_t)kMaxHypPerLaunch + kCullHdrWords + 2 * kCullStats; }
+inline CullBufs cull_bufs(int32_t* w, HypRec* h) {
+  constexpr size_t M = kMaxHypPerLaunch;
+  return CullBufs{w, w + M, w + 2 * M, w + 3 * M, w + 4 * M, w + 5 * M, h, h + M, w + 6 * M,
+                  reinterpret_cast<unsigned long long*>(w + 6 * M + kCullHdrWords)};
+}
+// what the launch leaves in res[0, D): the round's counts (culled hypotheses 0; *pick runs in the
+// tail and res[Dp + D] = hypotheses scored), or for dlg_score_benchmark the bound 32 nt_h of
+// every hypothesis, or the exact count of every scored hypothesis over the caller's fill
+enum CullMode { kCullRound = 0, kCullBenchBound = 1, kCullBenchCounts = 2 };
+// res = counts[Dp] | good[D] (counts zeroed by the caller); pstats: launch_score_pruned's stats,
+// fed by the exact passes
+void launch_score_culled(const SpatialView& v, const HypRec* hyps, int D, int Dp, int K, float cthr,
+                         float margin, int32_t* res, uint16_t* lp, int32_t* lp_n, int num_cus,
+                         hipStream_t s, unsigned long long* pstats, const CullBufs& cb,
+                         const PickArgs* pick, hipEvent_t ev_start, hipEvent_t ev_stop,
+                         CullMode mode);
 // (np_lim_max, the NORMAL_PLANE prefilter limit of the largest w: np_limit_host.hpp)
 // gather the pristine normals into the Morton-ordered copy: dst[i] = src[order[i]]
 void launch_gather_nrm(const float4* src, const int32_t* order, int64_t n, float4* dst,

@@ -144,6 +144,13 @@ class Context:
         return {"workgroups": a[0], "list_entries": a[1], "tiles": a[2], "blocks": a[3], "pairs": a[4],
                 "redecided_blocks": a[5], "wg_ticks_sum": a[6], "wg_ticks_max": a[7]}
 
+    def cull_stats(self, reset: bool = False) -> dict:
+        """The culled rounds' counters (DLG_OPT_CULL), kept on the device."""
+        a = (C.c_uint64 * 8)()
+        self.check(self._L.dlg_cull_stats(self.h, a, int(bool(reset))))
+        return {"rounds": a[0], "scored_a": a[1], "scored_b": a[2], "culled": a[3],
+                "rounds_with_b": a[4], "fallbacks": a[5]}
+
     def set_profiling(self, on=True):
         """on: True / 1 = all timing events, 2 = without the PCL refit walk's, False / 0 = none."""
         self.check(self._L.dlg_set_profiling(self.h, int(on)))

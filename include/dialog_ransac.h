@@ -54,7 +54,9 @@ extern "C" {
  * dlg_moving_least_squares, dlg_moving_least_squares_cloud, dlg_mls_params, dlg_mls_stats (same ABI
  * version: added entries); dlg_icp_align, dlg_icp_correspondences, dlg_icp_params_default,
  * dlg_icp_params, dlg_icp_stats, dlg_icp_iteration, DLG_OPT_ICP_REVERSED (same ABI version: added
- * entries and an added option); DLG_OPT_ICP_MAX_BLOCKS (same ABI version: an added option) */
+ * entries and an added option); DLG_OPT_ICP_MAX_BLOCKS (same ABI version: an added option);
+ * DLG_OPT_CULL, dlg_cull_stats, DLG_SCORE_BOUND / DLG_SCORE_CULLED (same ABI version: an added
+ * option, entry and benchmark ids) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -901,23 +903,47 @@ enum {
   DLG_OPT_ICP_REVERSED = 26,   /* dlg_icp_align / dlg_icp_correspondences: 1 = the correspondence
                                pass visits the working cloud from its last entry to its first.
                                Default 0.  Same bits for every value (the sums are exact) */
-  DLG_OPT_ICP_MAX_BLOCKS = 27  /* tests only, dlg_icp_align / dlg_icp_correspondences: n >= 1 = every
+  DLG_OPT_ICP_MAX_BLOCKS = 27, /* tests only, dlg_icp_align / dlg_icp_correspondences: n >= 1 = every
                                launch of the registration (gather, apply, level, moments, pack) runs
                                min(its default, n) workgroups, so that a small cloud takes the
                                several-entries-per-thread paths of a huge one; 0..65536.  Default 0
                                (the default launch shapes).  Same bits for every value (the sums
                                are exact) */
+  DLG_OPT_CULL = DLG_OPT_ICP_MAX_BLOCKS + 1 /* (28) probability-1 rounds of the plane models on one rank (pruned
+                               scoring, DLG_TILE_EXACT): 1 (default) = only the hypotheses whose
+                               tile bound -- 32 x the tiles whose sphere test they pass -- can
+                               still reach the best exact count are scored exactly, the 64 with the
+                               largest bounds first; n in 2..4096 = the n largest first (tests and
+                               A/B); 0 = every hypothesis.  A culled hypothesis has a count below
+                               the winner's, so computeModel's decision and everything after it are
+                               the same for every value; the counts of culled hypotheses are not
+                               computed (dlg_score_samples always computes all).  A round that
+                               scores more than 1/16 of its batch exactly turns culling off for the rest of
+                               the call */
 };
 enum { DLG_TILE_EXACT = 0, DLG_TILE_BF16 = 1, DLG_TILE_MFMA = 2 };
-enum { DLG_SCORE_EXACT = 0, DLG_SCORE_BF16 = 1, DLG_SCORE_PRUNED = 2 };
+enum { DLG_SCORE_EXACT = 0, DLG_SCORE_BF16 = 1, DLG_SCORE_PRUNED = 2,
+       /* dlg_score_benchmark only, the culled rounds' launches (DLG_OPT_CULL's K; 0 or 1: 64):
+        * DLG_SCORE_BOUND: counts_out[h] = the tile bound of hypothesis h (>= its count);
+        * DLG_SCORE_CULLED: counts_out[h] = the exact count of a scored hypothesis, -1 for a culled
+        * one (bad draws are never scored) */
+       DLG_SCORE_BOUND = 3, DLG_SCORE_CULLED = 4 };
 dlg_status dlg_ctx_set_option(dlg_ctx* ctx, int option, int64_t value);
 dlg_status dlg_ctx_get_option(const dlg_ctx* ctx, int option, int64_t* value);
 /* the pruned scoring kernel's counters since DLG_OPT_PRUNE_STATS was set (or the last reset):
  * [0] workgroups (DLG_TILE_EXACT), [1] super-tile list entries tested against tile spheres, [2] tiles visited,
  * [3] 32x32 blocks (DLG_TILE_EXACT: 64-lane passes) scored, [4] (tile, plane) pairs scored,
  * [5] blocks with a band re-decision (DLG_TILE_BF16 only), [6] / [7] (DLG_TILE_EXACT) the sum
- * and the maximum of the workgroups' spans in 100 MHz clock ticks (load balance) */
+ * and the maximum of the workgroups' spans in 100 MHz clock ticks (load balance).  A culled round
+ * (DLG_OPT_CULL) adds its exact passes: [1] planes tested against super-tile spheres, [2] tiles
+ * of the super-tiles visited, [4] (tile, plane) pairs evaluated, [3] those in passes of 128 */
 dlg_status dlg_prune_stats(dlg_ctx* ctx, uint64_t out[8], int reset);
+/* the culled rounds' counters since the context was created (or the last reset), kept on the
+ * device and read here: [0] rounds scored culled, [1] hypotheses scored in the first exact pass,
+ * [2] in the second, [3] good hypotheses culled, [4] rounds with a non-empty second pass,
+ * [5] rounds that scored more than 1/16 of their batch (culling then stops for the call); [6], [7] 0.
+ * dlg_score_benchmark's ids do not count */
+dlg_status dlg_cull_stats(dlg_ctx* ctx, uint64_t out[8], int reset);
 
 /* The shard of an n_global-point cloud rank `rank` of `world` should upload:
  * the contiguous range [*lo, *hi) of the global order, or -- when a shard would fall below the
