@@ -42,6 +42,7 @@ SYMBOLS = [
     "dlg_statistical_outlier_removal", "dlg_statistical_outlier_removal_cloud",
     "dlg_moving_least_squares", "dlg_moving_least_squares_cloud",
     "dlg_icp_params_default", "dlg_icp_align", "dlg_icp_correspondences", "dlg_cull_stats",
+    "dlg_fpfh_estimate", "dlg_cloud_fpfh",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -155,6 +156,18 @@ class IcpStats(C.Structure):
 class IcpIteration(C.Structure):
     _fields_ = [("n_corr", C.c_int64), ("mse", C.c_double), ("e", C.c_int32), ("e2", C.c_int32),
                 ("T", C.c_float * 16)]
+
+
+class FpfhParams(C.Structure):
+    _fields_ = [("search_radius", C.c_float)]
+
+
+class FpfhStats(C.Structure):
+    _fields_ = [("n_finite", C.c_int64), ("n_nan_rows", C.c_int64), ("n_zero_rows", C.c_int64),
+                ("max_neighbours", C.c_int64), ("n_lds_overflow", C.c_int64),
+                ("n_pairs", C.c_int64), ("n_pairs_failed", C.c_int64),
+                ("n_sum_literal", C.c_int64), ("device_ms", C.c_double), ("build_ms", C.c_double),
+                ("spfh_ms", C.c_double), ("weight_ms", C.c_double)]
 
 
 class SacParams(C.Structure):
@@ -302,6 +315,11 @@ def load():
                                 C.POINTER(IcpIteration), C.c_int64, C.POINTER(IcpStats)]
     L.dlg_icp_correspondences.argtypes = [vp, C.POINTER(Points), i32p, C.c_int64,
                                           C.POINTER(Points), fp, C.c_double, i32p, fp, i64p]
+    L.dlg_fpfh_estimate.argtypes = [vp, C.POINTER(Points), fp, C.c_int64, i32p, C.c_int64,
+                                    C.POINTER(FpfhParams), fp, C.c_int64, i32p, i32p,
+                                    C.POINTER(FpfhStats)]
+    L.dlg_cloud_fpfh.argtypes = [vp, vp, C.POINTER(FpfhParams), fp, C.c_int64, i32p,
+                                 C.POINTER(FpfhStats)]
     for s in SYMBOLS:
         if s not in ("dlg_abi_version", "dlg_status_string", "dlg_sac_params_default",
                      "dlg_last_error", "dlg_abi_struct_size", "dlg_icp_params_default"):

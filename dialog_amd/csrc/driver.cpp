@@ -167,6 +167,9 @@ int64_t dlg_abi_struct_size(int which) {
     case 13: return (int64_t)sizeof(dlg_icp_params);
     case 14: return (int64_t)sizeof(dlg_icp_stats);
     case 15: return (int64_t)sizeof(dlg_icp_iteration);
+    // (16 is left unassigned)
+    case 17: return (int64_t)sizeof(dlg_fpfh_params);
+    case 18: return (int64_t)sizeof(dlg_fpfh_stats);
   }
   return -1;
 }
@@ -290,6 +293,7 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   c->sw.release();
   c->mw.release();
   c->iw.release();
+  c->fw.release();
   c->pstats.release();
   c->cull_i.release();
   c->cull_h.release();

@@ -197,6 +197,19 @@ struct MlsWork {
   }
 };
 
+// scratch of the FPFH descriptors (fpfh_host.cpp; the points and the grid are the normals path's
+// nw.x/y/z and nw.lv[0], the normals nw.nrm)
+struct FpfhWork {
+  DevBuf<float4> snrm;             // the normals in the grid's sorted order
+  DevBuf<float> spfh, hist;        // n x 33 SPFH table; one 33-float row per list entry
+  DevBuf<int32_t> lst, cnt, pairs, counts, o_nb;
+  DevBuf<unsigned long long> acc;
+  void release() {
+    snrm.release(); spfh.release(); hist.release(); lst.release(); cnt.release(); pairs.release();
+    counts.release(); o_nb.release(); acc.release();
+  }
+};
+
 // scratch of the rigid registration (icp_host.cpp; the finite target points and their hierarchy are
 // the normals path's nw.x/y/z and nw.lv[])
 struct IcpWork {
@@ -377,6 +390,7 @@ struct dlg_ctx {
   SorWork sw;
   MlsWork mw;
   IcpWork iw;
+  FpfhWork fw;
   // PCL float refit on the device (fsum.hip): scratch sized for fs_cap inliers
   DevBuf<uint8_t> fs_scr;
   // the spatial index build's sort scratch (Morton keys and orders, ping-pong; radix-sort

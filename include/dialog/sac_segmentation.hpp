@@ -20,7 +20,9 @@
 //   * pcl::StatisticalOutlierRemoval<PointT> (PCLViewer.cpp:334-358) ->
 //     dialog::StatisticalOutlierRemoval<PointT>;
 //   * pcl::MovingLeastSquares<PointInT, PointOutT> (PCLViewer.cpp:387-423, "rebuild plane") ->
-//     dialog::MovingLeastSquares<PointInT, PointOutT>.
+//     dialog::MovingLeastSquares<PointInT, PointOutT>;
+//   * pcl::FPFHEstimation<PointInT, PointNT, pcl::FPFHSignature33> (PCLViewer.cpp:524-543, the
+//     descriptors of "registration") -> dialog::FPFHEstimation<PointInT, PointNT, PointOutT>.
 // With real PCL available define DIALOG_HAVE_PCL before including; otherwise minimal
 // layout-identical stand-ins for pcl::PointXYZ (16 B), pcl::Normal (32 B), pcl::PointNormal (48 B),
 // pcl::PointCloud, pcl::ModelCoefficients and pcl::PointIndices are declared here.
@@ -596,6 +598,75 @@ class MovingLeastSquares {
   dlg_mls_params prm_{0.0f, 0, 2, 0, 0.0};
   dlg_mls_stats stats_{};
   pcl::PointIndices::Ptr corresponding_;
+};
+
+// pcl::FPFHSignature33's layout (pcl::FPFHSignature33 itself works as PointOutT too)
+struct FPFHSignature33 {
+  float histogram[33];
+};
+
+// pcl::FPFHEstimation<PointInT, PointNT, PointOutT> with setRadiusSearch (PCLViewer.cpp:524-543):
+// one descriptor per point of the input cloud, or per index; the search surface is the input
+// cloud.  PointNT needs normal_x / normal_y / normal_z first in its record (pcl::Normal,
+// pcl::PointNormal's are not: pass pcl::Normal), PointOutT a float histogram[33].  A non-finite
+// entry gets 33 NaNs (and output.is_dense = false), one with no neighbour but itself 33 zeros.
+template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33>
+class FPFHEstimation {
+ public:
+  typedef typename pcl::PointCloud<PointInT>::ConstPtr PointCloudInConstPtr;
+  typedef typename pcl::PointCloud<PointNT>::ConstPtr PointCloudNConstPtr;
+  explicit FPFHEstimation(Context* ctx = nullptr) : ctx_(ctx) {}
+  void setInputCloud(const PointCloudInConstPtr& cloud) { input_ = cloud; }
+  void setInputNormals(const PointCloudNConstPtr& normals) { normals_ = normals; }
+  void setIndices(const pcl::PointIndices::Ptr& idx) { indices_ = idx ? idx->indices : std::vector<int>(); has_idx_ = (bool)idx; }
+  void setIndices(const std::vector<int>& idx) { indices_ = idx; has_idx_ = true; }
+  template <typename TreePtr>
+  void setSearchMethod(const TreePtr&) {}
+  void setRadiusSearch(double r) { prm_.search_radius = (float)r; }
+  double getRadiusSearch() const { return prm_.search_radius; }
+  const dlg_fpfh_stats& lastStats() const { return stats_; }
+
+  void compute(pcl::PointCloud<PointOutT>& output) {
+    static_assert(sizeof(((PointOutT*)nullptr)->histogram) == 33 * sizeof(float),
+                  "PointOutT::histogram must be float[33]");
+    stats_ = dlg_fpfh_stats{};
+    output.points.clear();
+    output.width = 0;
+    output.height = 1;
+    output.is_dense = true;
+    if (!input_ || !normals_) {
+      std::fprintf(stderr, "[dialog::FPFHEstimation::compute] No input dataset or normals given!\n");
+      return;
+    }
+    if (normals_->points.size() != input_->points.size()) {
+      std::fprintf(stderr, "[dialog::FPFHEstimation::compute] The number of points differs from "
+                           "the number of normals!\n");
+      return;
+    }
+    std::vector<int32_t> idx32(indices_.begin(), indices_.end());
+    const int64_t n = has_idx_ ? (int64_t)idx32.size() : (int64_t)input_->points.size();
+    // (an empty index list has a null data(): the C ABI would read "no indices")
+    if (n == 0 || input_->points.empty()) return;
+    dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    dlg_points pts{&input_->points[0].x, (int64_t)input_->points.size(), (int64_t)sizeof(PointInT)};
+    output.points.resize((size_t)n);
+    check(dlg_fpfh_estimate(c, &pts, &normals_->points[0].normal_x, (int64_t)sizeof(PointNT),
+                            has_idx_ ? idx32.data() : nullptr, n, &prm_,
+                            &output.points[0].histogram[0], (int64_t)sizeof(PointOutT), nullptr,
+                            nullptr, &stats_),
+          c);
+    output.width = (uint32_t)n;
+    output.is_dense = stats_.n_nan_rows == 0;
+  }
+
+ private:
+  Context* ctx_;
+  PointCloudInConstPtr input_;
+  PointCloudNConstPtr normals_;
+  std::vector<int> indices_;
+  bool has_idx_ = false;
+  dlg_fpfh_params prm_{0.0f};
+  dlg_fpfh_stats stats_{};
 };
 
 // A row-major 4x4 float matrix: what getFinalTransformation returns here (no Eigen): m(r, c).

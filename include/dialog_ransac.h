@@ -56,7 +56,8 @@ extern "C" {
  * dlg_icp_params, dlg_icp_stats, dlg_icp_iteration, DLG_OPT_ICP_REVERSED (same ABI version: added
  * entries and an added option); DLG_OPT_ICP_MAX_BLOCKS (same ABI version: an added option);
  * DLG_OPT_CULL, dlg_cull_stats, DLG_SCORE_BOUND / DLG_SCORE_CULLED (same ABI version: an added
- * option, entry and benchmark ids) */
+ * option, entry and benchmark ids); dlg_fpfh_estimate, dlg_cloud_fpfh, dlg_fpfh_params,
+ * dlg_fpfh_stats (same ABI version: added entries) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -166,7 +167,8 @@ int dlg_abi_version(void);
 /* sizeof of the ABI's structs, for bindings to check their layouts: 0 dlg_points, 1 dlg_sac_params,
  * 2 dlg_sac_stats, 3 dlg_extract_stats, 4 dlg_planes, 5 dlg_postprocess_params, 6 dlg_voxel_params,
  * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats, 10 dlg_mls_params, 11 dlg_mls_stats,
- * 13 dlg_icp_params, 14 dlg_icp_stats, 15 dlg_icp_iteration (12 is unassigned); -1 otherwise */
+ * 13 dlg_icp_params, 14 dlg_icp_stats, 15 dlg_icp_iteration, 17 dlg_fpfh_params, 18 dlg_fpfh_stats
+ * (12 and 16 are unassigned); -1 otherwise */
 int64_t dlg_abi_struct_size(int which);
 
 /* ---- contexts ------------------------------------------------------------------------------ */
@@ -618,6 +620,77 @@ dlg_status dlg_icp_correspondences(dlg_ctx* ctx, const dlg_points* src, const in
                                    int64_t n_indices, const dlg_points* tgt, const float* transform,
                                    double max_dist, int32_t* nn_out, float* d2_out,
                                    int64_t* n_corr);
+
+/* ---- FPFH descriptors (Dialog/PCLViewer.cpp:524-543, "registration" before SAC-IA) ------------ */
+/* pcl::FPFHEstimation<pcl::PointXYZ, pcl::Normal, pcl::FPFHSignature33>::compute with
+ * setRadiusSearch, the search surface being the input cloud, over the list indices[0..n_indices)
+ * (any order, duplicates allowed; NULL: 0..n-1).  PCL 1.8's computePairFeatures,
+ * computePointSPFHSignature and weightPointSPFHSignature restated (from memory: parity unpinned,
+ * DESIGN.md section 2).  All arithmetic float unless marked double:
+ *   the search structure holds every finite point of the cloud, listed or not;
+ *   the neighbours of a point: KdTreeFLANN's radius search, float ((0 + dx^2) + dy^2) + dz^2 <
+ *   (float)((double)r * (double)r), the point included, in (d2, index) order; m = their number;
+ *   pair features of (p, n_p) = the SPFH's own point and (q, n_q) = a neighbour: d = q - p, f4 =
+ *   sqrt((dx^2 + dy^2) + dz^2), 0: the pair fails; a1 = (n_p . d) / f4, a2 = (n_q . d) / f4 (dots
+ *   summed left to right); acos(|a1|) > acos(|a2|): u = n_q, t = n_p, d = -d, f3 = -a2, otherwise
+ *   u = n_p, t = n_q, f3 = a1; v = d x u, |v| = sqrt of its squared norm, 0: the pair fails;
+ *   v /= |v|; w = u x v; f2 = v . t; f1 = atan2(w . t, u . t);
+ *   acos and atan2 are the correctly rounded floats of the real functions (the one definition that
+ *   does not depend on a maths library; unpinned against PCL's libm);
+ *   SPFH of a point, three 11-bin histograms: incr = 100.0f / float(m - 1); every neighbour other
+ *   than the point itself (by index) whose pair does not fail adds incr to bin
+ *   floor(11 ((f1 + M_PI) d_pi)), floor(11 ((f2 + 1.0) 0.5)) and floor(11 ((f3 + 1.0) 0.5)) of the
+ *   three (double; d_pi = 1.0f / (2.0f * float(M_PI)); clamped to 0..10, a NaN to 0): a bin's value
+ *   is the c-fold sequential float sum of incr, c = its count.  A pair in which either normal has a
+ *   non-finite component adds nothing (PCL casts a NaN to int there: undefined, unpinned);
+ *   FPFH of a list entry: its neighbours in (d2, index) order, those with d2 == 0 skipped; w =
+ *   1.0f / d2; per bin val = spfh[neighbour][b] * w, hist[b] += val (float), sum_g += val (double,
+ *   g = the bin's histogram), neighbour-major and bin-minor; then hist[b] *= (float)(100.0 / sum_g)
+ *   for each g with sum_g != 0.
+ * normals: one record of normals_stride_bytes (>= 12, a multiple of 4) per point, nx, ny, nz first.
+ * hist_out: one record of hist_stride_bytes (>= 132, a multiple of 4) per list entry, 33 floats
+ * first (the rest of a record is not written); 33 quiet NaNs for an entry with a non-finite
+ * coordinate, 33 zeros for one with no neighbour but itself.  neighbours (nullable): one per list
+ * entry, m, -1 for a non-finite entry.  spfh_counts (nullable): n x 33 int32, the integer bin counts
+ * of every finite point's SPFH (rows of non-finite points are zero).
+ * DLG_ERR_INVALID: a search_radius that is not finite and > 0, an index outside [0, n), n or
+ * n_indices above INT32_MAX, null normals, a bad stride, a context of a communicator with world > 1
+ * (one rank's shard lacks the neighbours across the cut). */
+typedef struct {
+  float search_radius;      /* setRadiusSearch; finite and > 0 */
+} dlg_fpfh_params;          /* dlg_abi_struct_size(17) */
+
+typedef struct {
+  int64_t n_finite;         /* finite points of the cloud */
+  int64_t n_nan_rows;       /* list entries with a non-finite coordinate (rows of NaNs) */
+  int64_t n_zero_rows;      /* finite list entries with no neighbour but themselves */
+  int64_t max_neighbours;   /* the largest neighbour count of a finite list entry */
+  int64_t n_lds_overflow;   /* finite list entries with more neighbours than the weighting kernel's
+                               on-chip buffer holds (sorted and walked in several windows) */
+  int64_t n_pairs;          /* pairs that added to the SPFH of a finite list entry (per entry) */
+  int64_t n_pairs_failed;   /* the other neighbours of those entries, themselves excluded: failed
+                               pairs and pairs with a non-finite normal */
+  int64_t n_sum_literal;    /* finite list entries whose double sums took the literal loop (the
+                               exactness certificate of DESIGN.md section 5j missed) */
+  double device_ms;         /* HIP events around the call's device work when profiling is on (the
+                               copies in and out excluded, the small read-backs between included) */
+  double build_ms;          /* ... its parts: the grid build, */
+  double spfh_ms;           /*     the SPFH pass (with the gather of the normals), */
+  double weight_ms;         /*     the weighting pass */
+} dlg_fpfh_stats;           /* dlg_abi_struct_size(18) */
+
+dlg_status dlg_fpfh_estimate(dlg_ctx* ctx, const dlg_points* pts, const float* normals,
+                             int64_t normals_stride_bytes, const int32_t* indices,
+                             int64_t n_indices, const dlg_fpfh_params* params, float* hist_out,
+                             int64_t hist_stride_bytes, int32_t* neighbours, int32_t* spfh_counts,
+                             dlg_fpfh_stats* stats);
+/* The same descriptors of every point of a cloud's device copy (upload order) with its attached
+ * normals (dlg_cloud_set_normals, dlg_cloud_estimate_normals, dlg_cloud_regulate_normals): upload ->
+ * normals -> FPFH has no host round trip on the input side.  DLG_ERR_INVALID when no normals are
+ * attached. */
+dlg_status dlg_cloud_fpfh(dlg_ctx* ctx, dlg_cloud* cloud, const dlg_fpfh_params* params,
+                          float* hist_out, int64_t hist_stride_bytes, int32_t* neighbours,
+                          dlg_fpfh_stats* stats);
 
 /* ---- postProcessPlanes (Dialog/PlaneDetect.h:1454-1579) ------------------------------------ */
 /* The final planes (plane_clouds_final, HeaderFile.h:98; struct Plane HeaderFile.h:81-88) as
