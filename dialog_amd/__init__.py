@@ -17,7 +17,8 @@ from .preprocess import (preprocess, remove_redundant_points, voxel_grid,  # noq
                          voxel_grid_cloud, statistical_outlier_removal,
                          statistical_outlier_removal_cloud, moving_least_squares,
                          moving_least_squares_cloud)
-from .registration import icp_align, icp_correspondences  # noqa: F401
+from .registration import (fpfh_knn, icp_align, icp_correspondences,  # noqa: F401
+                           sac_ia_align, sac_ia_score)
 from .features import cloud_fpfh, fpfh_estimation  # noqa: F401
 from .postprocess import (PostProcessParams, cluster_filter, plane_border,  # noqa: F401
                           post_process_planes, refit_planes)
@@ -39,4 +40,5 @@ __all__ = ["Context", "Cloud", "SACSegmentation", "extract_planes", "segment_clo
            "SACMODEL_PARALLEL_PLANE", "score_samples", "voxel_grid", "voxel_grid_cloud",
            "statistical_outlier_removal", "statistical_outlier_removal_cloud",
            "moving_least_squares", "moving_least_squares_cloud", "icp_align",
-           "icp_correspondences", "fpfh_estimation", "cloud_fpfh"]
+           "icp_correspondences", "fpfh_estimation", "cloud_fpfh", "sac_ia_align", "sac_ia_score",
+           "fpfh_knn"]

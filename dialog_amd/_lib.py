@@ -43,6 +43,7 @@ SYMBOLS = [
     "dlg_moving_least_squares", "dlg_moving_least_squares_cloud",
     "dlg_icp_params_default", "dlg_icp_align", "dlg_icp_correspondences", "dlg_cull_stats",
     "dlg_fpfh_estimate", "dlg_cloud_fpfh",
+    "dlg_sac_ia_params_default", "dlg_fpfh_knn", "dlg_sac_ia_score", "dlg_sac_ia_align",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -168,6 +169,30 @@ class FpfhStats(C.Structure):
                 ("n_pairs", C.c_int64), ("n_pairs_failed", C.c_int64),
                 ("n_sum_literal", C.c_int64), ("device_ms", C.c_double), ("build_ms", C.c_double),
                 ("spfh_ms", C.c_double), ("weight_ms", C.c_double)]
+
+
+class SacIaParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("nr_samples", C.c_int32),
+                ("k_correspondences", C.c_int32), ("rng", C.c_int32), ("seed", C.c_uint32),
+                ("compute_fitness", C.c_int32), ("batch", C.c_int32), ("max_blocks", C.c_int32),
+                ("min_sample_distance", C.c_float), ("max_correspondence_distance", C.c_double),
+                ("fitness_max_range", C.c_double)]
+
+
+class SacIaHypothesis(C.Structure):
+    _fields_ = [("sample", C.c_int32 * 8), ("match", C.c_int32 * 8), ("rank", C.c_int32 * 8),
+                ("valid", C.c_int32), ("relaxations", C.c_int32), ("draws", C.c_int64),
+                ("T", C.c_float * 16), ("err_hi", C.c_uint64), ("err_lo", C.c_uint64),
+                ("n_far", C.c_int64), ("n_used", C.c_int64)]
+
+
+class SacIaStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("best_iteration", C.c_int32),
+                ("n_valid", C.c_int32), ("n_invalid", C.c_int32), ("batches", C.c_int32),
+                ("levels", C.c_int32), ("reserved", C.c_int32), ("draws", C.c_int64),
+                ("relaxations", C.c_int64), ("n_queries", C.c_int64), ("host_syncs", C.c_int64),
+                ("error", C.c_double), ("fitness", C.c_double), ("build_ms", C.c_double),
+                ("knn_ms", C.c_double), ("score_ms", C.c_double), ("device_ms", C.c_double)]
 
 
 class SacParams(C.Structure):
@@ -320,9 +345,19 @@ def load():
                                     C.POINTER(FpfhStats)]
     L.dlg_cloud_fpfh.argtypes = [vp, vp, C.POINTER(FpfhParams), fp, C.c_int64, i32p,
                                  C.POINTER(FpfhStats)]
+    L.dlg_sac_ia_params_default.argtypes = [C.POINTER(SacIaParams)]
+    L.dlg_sac_ia_params_default.restype = None
+    L.dlg_fpfh_knn.argtypes = [vp, fp, C.c_int64, C.c_int64, fp, C.c_int64, C.c_int64, C.c_int32,
+                               i32p, fp]
+    L.dlg_sac_ia_score.argtypes = [vp, C.POINTER(Points), C.POINTER(Points), fp, C.c_int64,
+                                   C.c_double, C.c_int32, C.c_int32, C.POINTER(SacIaHypothesis)]
+    L.dlg_sac_ia_align.argtypes = [vp, C.POINTER(Points), fp, C.c_int64, C.POINTER(Points), fp,
+                                   C.c_int64, C.POINTER(SacIaParams), fp, fp, fp, C.c_int64,
+                                   C.POINTER(SacIaHypothesis), C.c_int64, C.POINTER(SacIaStats)]
     for s in SYMBOLS:
         if s not in ("dlg_abi_version", "dlg_status_string", "dlg_sac_params_default",
-                     "dlg_last_error", "dlg_abi_struct_size", "dlg_icp_params_default"):
+                     "dlg_last_error", "dlg_abi_struct_size", "dlg_icp_params_default",
+                     "dlg_sac_ia_params_default"):
             getattr(L, s).restype = C.c_int
     _lib = L
     return L

@@ -170,6 +170,9 @@ int64_t dlg_abi_struct_size(int which) {
     // (16 is left unassigned)
     case 17: return (int64_t)sizeof(dlg_fpfh_params);
     case 18: return (int64_t)sizeof(dlg_fpfh_stats);
+    case 19: return (int64_t)sizeof(dlg_sac_ia_params);
+    case 20: return (int64_t)sizeof(dlg_sac_ia_hypothesis);
+    case 21: return (int64_t)sizeof(dlg_sac_ia_stats);
   }
   return -1;
 }
@@ -294,6 +297,7 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   c->mw.release();
   c->iw.release();
   c->fw.release();
+  c->aw.release();
   c->pstats.release();
   c->cull_i.release();
   c->cull_h.release();

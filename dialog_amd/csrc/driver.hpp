@@ -226,6 +226,23 @@ struct IcpWork {
   }
 };
 
+// scratch of the SAC-IA initial alignment (sacia_host.cpp; the valid target points and their
+// hierarchy are the normals path's nw.x/y/z and nw.lv[])
+struct SaciaWork {
+  DevBuf<uint8_t> flags, pflags, state;  // valid rows; valid points; one SaciaState (sacia.hpp)
+  DevBuf<float> tx, ty, tz, sx, sy, sz;  // the target's and the source's points, de-interleaved
+  DevBuf<float> rows, queries, part_d, knn_d, xfs;
+  DevBuf<int32_t> fin_pos, part_i, knn_i;
+  DevBuf<unsigned long long> qa, qb, acc;
+  void release() {
+    flags.release(); pflags.release(); state.release();
+    tx.release(); ty.release(); tz.release(); sx.release(); sy.release(); sz.release();
+    rows.release(); queries.release(); part_d.release(); knn_d.release(); xfs.release();
+    fin_pos.release(); part_i.release(); knn_i.release();
+    qa.release(); qb.release(); acc.release();
+  }
+};
+
 }  // namespace dlg
 
 using namespace dlg;
@@ -391,6 +408,7 @@ struct dlg_ctx {
   MlsWork mw;
   IcpWork iw;
   FpfhWork fw;
+  SaciaWork aw;
   // PCL float refit on the device (fsum.hip): scratch sized for fs_cap inliers
   DevBuf<uint8_t> fs_scr;
   // the spatial index build's sort scratch (Morton keys and orders, ping-pong; radix-sort
@@ -514,5 +532,10 @@ void release_cloud_buffers(dlg_cloud* cl);
 // normals on the device -> the cloud (dlg_cloud_set_normals, dlg_cloud_estimate_normals)
 void attach_normals(dlg_ctx* c, dlg_cloud* cl, const float* raw_dev, int64_t stride_f,
                     int curv_off, bool by_pos);
+
+// getFitnessScore(max_range) of src moved through the row-major 4x4 xf16 against tgt, by
+// dlg_icp_align's own pass (icp_host.cpp; it builds the target's hierarchy again)
+double icp_fitness(dlg_ctx* c, const dlg_points* src, const dlg_points* tgt, const float* xf16,
+                   double max_range);
 
 }  // namespace dlg

@@ -170,7 +170,24 @@ int64_t to_digits(const IcpState& s, int64_t* dig) {
   return dig[0];
 }
 
+// getFitnessScore from a pass that kept d2 <= max_range: DBL_MAX when nothing was kept
+double fitness_of(const IcpState& s) {
+  int64_t dig[kIcpDigits];
+  const int64_t k = to_digits(s, dig);
+  if (k <= 0) return DBL_MAX;
+  const IcpMoments mo = icp_moments(dig);
+  return mo.D / (double)k * pow2d(icp_qexp(bits_float(s.d2max)) - kFastBits);
+}
+
 }  // namespace
+
+double icp_fitness(dlg_ctx* c, const dlg_points* src, const dlg_points* tgt, const float* xf16,
+                   double max_range) {
+  IcpCall ic(c);
+  ic.setup(src, nullptr, 0, tgt, xf16);
+  return fitness_of(ic.pass(IcpXf{}, 0, std::isnan(max_range) ? -1.0 : max_range));
+}
+
 }  // namespace dlg
 
 extern "C" {
@@ -247,12 +264,7 @@ dlg_status dlg_icp_align(dlg_ctx* c, const dlg_points* src, const int32_t* indic
       // (d2 <= max_range is "not d2 > max_range": the pass's own test)
       const IcpState& s = ic.pass(xf, pending, std::isnan(mr) ? -1.0 : mr);
       pending = 0;
-      const int64_t k = to_digits(s, dig);
-      fitness = DBL_MAX;
-      if (k > 0) {
-        const IcpMoments mo = icp_moments(dig);
-        fitness = mo.D / (double)k * pow2d(icp_qexp(bits_float(s.d2max)) - kFastBits);
-      }
+      fitness = fitness_of(s);
     }
     if (pending)
       launch_icp_apply(xf, v.wx.p, v.wy.p, v.wz.p, ic.m, c->opt.icp_max_blocks, c->stream);

@@ -678,6 +678,35 @@ struct Matrix4f {
   static Matrix4f Identity() { return Matrix4f(); }
 };
 
+// Registration::getFitnessScore(max_range): the mean squared distance of the aligned points to
+// their nearest target points, over those with d2 <= max_range (DBL_MAX when there is none), summed
+// as dlg_icp_align sums its mse.
+inline double registration_fitness(dlg_ctx* c, const dlg_points& src, const dlg_points& tgt,
+                                   double max_dist, double max_range) {
+  const int64_t n = src.n;
+  std::vector<int32_t> nn((size_t)n);
+  std::vector<float> d2((size_t)n);
+  int64_t k = 0;
+  check(dlg_icp_correspondences(c, &src, nullptr, 0, &tgt, nullptr,
+                                max_dist, nn.data(), d2.data(), &k),
+        c);
+  float dmax = 0.0f;
+  int64_t kept = 0;
+  for (int64_t i = 0; i < n; ++i)
+    if (nn[(size_t)i] >= 0 && (double)d2[(size_t)i] <= max_range) {
+      ++kept;
+      if (d2[(size_t)i] > dmax) dmax = d2[(size_t)i];
+    }
+  if (kept == 0) return std::numeric_limits<double>::max();
+  int e2 = 0;
+  if (dmax > 0.0f) (void)std::frexp((double)dmax, &e2);
+  unsigned __int128 sum = 0;
+  for (int64_t i = 0; i < n; ++i)
+    if (nn[(size_t)i] >= 0 && (double)d2[(size_t)i] <= max_range)
+      sum += (unsigned __int128)(uint64_t)std::trunc(std::ldexp((double)d2[(size_t)i], 48 - e2));
+  return std::ldexp((double)sum / (double)kept, e2 - 48);
+}
+
 // pcl::IterativeClosestPoint<PointSource, PointTarget> as the reference calls it
 // (PCLViewer.cpp:581-636): setInputSource / setInputTarget / setMaximumIterations /
 // setMaxCorrespondenceDistance / setTransformationEpsilon / setEuclideanFitnessEpsilon /
@@ -720,27 +749,7 @@ class IterativeClosestPoint {
     const int64_t n = (int64_t)aligned_.size() / 3;
     dlg_points src{aligned_.data(), n, 12};
     dlg_points tgt = target_points();
-    std::vector<int32_t> nn((size_t)n);
-    std::vector<float> d2((size_t)n);
-    int64_t k = 0;
-    check(dlg_icp_correspondences(c, &src, nullptr, 0, &tgt, nullptr,
-                                  prm_default_.max_correspondence_distance, nn.data(), d2.data(), &k),
-          c);
-    float dmax = 0.0f;
-    int64_t kept = 0;
-    for (int64_t i = 0; i < n; ++i)
-      if (nn[(size_t)i] >= 0 && (double)d2[(size_t)i] <= max_range) {
-        ++kept;
-        if (d2[(size_t)i] > dmax) dmax = d2[(size_t)i];
-      }
-    if (kept == 0) return std::numeric_limits<double>::max();
-    int e2 = 0;
-    if (dmax > 0.0f) (void)std::frexp((double)dmax, &e2);
-    unsigned __int128 sum = 0;
-    for (int64_t i = 0; i < n; ++i)
-      if (nn[(size_t)i] >= 0 && (double)d2[(size_t)i] <= max_range)
-        sum += (unsigned __int128)(uint64_t)std::trunc(std::ldexp((double)d2[(size_t)i], 48 - e2));
-    return std::ldexp((double)sum / (double)kept, e2 - 48);
+    return registration_fitness(c, src, tgt, prm_default_.max_correspondence_distance, max_range);
   }
 
  private:
@@ -791,6 +800,112 @@ class IterativeClosestPoint {
   dlg_icp_params prm_{};
   dlg_icp_params prm_default_ = [] { dlg_icp_params p; dlg_icp_params_default(&p); return p; }();
   dlg_icp_stats stats_{};
+  Matrix4f final_;
+  std::vector<float> aligned_;
+};
+
+// pcl::SampleConsensusInitialAlignment<PointSource, PointTarget, FeatureT> as the reference calls it
+// (PCLViewer.cpp:546-558): setInputSource / setSourceFeatures / setInputTarget / setTargetFeatures,
+// align(output[, guess]), hasConverged, getFitnessScore, getFinalTransformation (dlg_sac_ia_align).
+// FeatureT needs a float histogram[33] first in its record.  setRandGenerator / setRandSeed are
+// not PCL's: rand() is glibc's (0) or the Visual C++ runtime's (1), seeded as srand would.
+template <typename PointSource, typename PointTarget, typename FeatureT = FPFHSignature33>
+class SampleConsensusInitialAlignment {
+ public:
+  typedef typename pcl::PointCloud<PointSource>::ConstPtr PointCloudSourceConstPtr;
+  typedef typename pcl::PointCloud<PointTarget>::ConstPtr PointCloudTargetConstPtr;
+  typedef typename pcl::PointCloud<FeatureT>::ConstPtr FeatureCloudConstPtr;
+  explicit SampleConsensusInitialAlignment(Context* ctx = nullptr) : ctx_(ctx) {
+    dlg_sac_ia_params_default(&prm_);
+  }
+  void setInputSource(const PointCloudSourceConstPtr& cloud) { source_ = cloud; }
+  void setInputTarget(const PointCloudTargetConstPtr& cloud) { target_ = cloud; }
+  void setSourceFeatures(const FeatureCloudConstPtr& f) { source_features_ = f; }
+  void setTargetFeatures(const FeatureCloudConstPtr& f) { target_features_ = f; }
+  void setMinSampleDistance(float d) { prm_.min_sample_distance = d; }
+  float getMinSampleDistance() const { return prm_.min_sample_distance; }
+  void setNumberOfSamples(int n) { prm_.nr_samples = n; }
+  int getNumberOfSamples() const { return prm_.nr_samples; }
+  void setCorrespondenceRandomness(int k) { prm_.k_correspondences = k; }
+  int getCorrespondenceRandomness() const { return prm_.k_correspondences; }
+  void setMaximumIterations(int n) { prm_.max_iterations = n; }
+  int getMaximumIterations() const { return prm_.max_iterations; }
+  void setMaxCorrespondenceDistance(double d) { prm_.max_correspondence_distance = d; }
+  double getMaxCorrespondenceDistance() const { return prm_.max_correspondence_distance; }
+  void setRandGenerator(int rng) { prm_.rng = rng; }
+  void setRandSeed(uint32_t seed) { prm_.seed = seed; }
+  bool hasConverged() const { return stats_.converged != 0; }
+  Matrix4f getFinalTransformation() const { return final_; }
+  const dlg_sac_ia_stats& lastStats() const { return stats_; }
+
+  void align(pcl::PointCloud<PointSource>& output) { align_impl(output, nullptr); }
+  void align(pcl::PointCloud<PointSource>& output, const Matrix4f& guess) {
+    align_impl(output, guess.data());
+  }
+
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) {
+    if (!target_ || aligned_.empty()) return std::numeric_limits<double>::max();
+    dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    dlg_points src{aligned_.data(), (int64_t)aligned_.size() / 3, 12};
+    dlg_icp_params icp;
+    dlg_icp_params_default(&icp);
+    return registration_fitness(c, src, target_points(), icp.max_correspondence_distance, max_range);
+  }
+
+ private:
+  dlg_points target_points() const {
+    return dlg_points{target_->points.empty() ? nullptr : &target_->points[0].x,
+                      (int64_t)target_->points.size(), (int64_t)sizeof(PointTarget)};
+  }
+  void align_impl(pcl::PointCloud<PointSource>& output, const float* guess) {
+    // (output may be the source cloud itself, as at PCLViewer.cpp:553: it is written last)
+    stats_ = dlg_sac_ia_stats{};
+    final_ = Matrix4f();
+    aligned_.clear();
+    if (!source_ || !target_ || !source_features_ || !target_features_) {
+      std::fprintf(stderr, "[dialog::SampleConsensusInitialAlignment::align] No input source, "
+                           "target or features!\n");
+      output.points.clear();
+      output.width = 0;
+      output.height = 1;
+      output.is_dense = true;
+      return;
+    }
+    if (source_features_->points.size() != source_->points.size() ||
+        target_features_->points.size() != target_->points.size())
+      throw Error(DLG_ERR_INVALID, "SampleConsensusInitialAlignment: one feature per point");
+    dlg_ctx* c = (ctx_ ? ctx_ : &Context::thread_default())->get();
+    dlg_points src{source_->points.empty() ? nullptr : &source_->points[0].x,
+                   (int64_t)source_->points.size(), (int64_t)sizeof(PointSource)};
+    dlg_points tgt = target_points();
+    const int64_t n = src.n;
+    aligned_.resize((size_t)n * 3);
+    check(dlg_sac_ia_align(
+              c, &src, n > 0 ? &source_features_->points[0].histogram[0] : nullptr,
+              (int64_t)sizeof(FeatureT), &tgt,
+              tgt.n > 0 ? &target_features_->points[0].histogram[0] : nullptr,
+              (int64_t)sizeof(FeatureT), &prm_, guess, final_.v, n > 0 ? aligned_.data() : nullptr,
+              12, nullptr, 0, &stats_),
+          c);
+    std::vector<PointSource> moved(source_->points.begin(), source_->points.end());
+    bool dense = true;
+    for (int64_t i = 0; i < n; ++i) {
+      PointSource& o = moved[(size_t)i];
+      o.x = aligned_[3 * i]; o.y = aligned_[3 * i + 1]; o.z = aligned_[3 * i + 2];
+      dense = dense && std::isfinite(o.x) && std::isfinite(o.y) && std::isfinite(o.z);
+    }
+    output.points.assign(moved.begin(), moved.end());
+    output.width = (uint32_t)n;
+    output.height = 1;
+    output.is_dense = dense;
+  }
+
+  Context* ctx_;
+  PointCloudSourceConstPtr source_;
+  PointCloudTargetConstPtr target_;
+  FeatureCloudConstPtr source_features_, target_features_;
+  dlg_sac_ia_params prm_{};
+  dlg_sac_ia_stats stats_{};
   Matrix4f final_;
   std::vector<float> aligned_;
 };

@@ -57,7 +57,9 @@ extern "C" {
  * entries and an added option); DLG_OPT_ICP_MAX_BLOCKS (same ABI version: an added option);
  * DLG_OPT_CULL, dlg_cull_stats, DLG_SCORE_BOUND / DLG_SCORE_CULLED (same ABI version: an added
  * option, entry and benchmark ids); dlg_fpfh_estimate, dlg_cloud_fpfh, dlg_fpfh_params,
- * dlg_fpfh_stats (same ABI version: added entries) */
+ * dlg_fpfh_stats (same ABI version: added entries); dlg_sac_ia_align, dlg_sac_ia_score,
+ * dlg_fpfh_knn, dlg_sac_ia_params_default, dlg_sac_ia_params, dlg_sac_ia_hypothesis,
+ * dlg_sac_ia_stats (same ABI version: added entries) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -167,8 +169,9 @@ int dlg_abi_version(void);
 /* sizeof of the ABI's structs, for bindings to check their layouts: 0 dlg_points, 1 dlg_sac_params,
  * 2 dlg_sac_stats, 3 dlg_extract_stats, 4 dlg_planes, 5 dlg_postprocess_params, 6 dlg_voxel_params,
  * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats, 10 dlg_mls_params, 11 dlg_mls_stats,
- * 13 dlg_icp_params, 14 dlg_icp_stats, 15 dlg_icp_iteration, 17 dlg_fpfh_params, 18 dlg_fpfh_stats
- * (12 and 16 are unassigned); -1 otherwise */
+ * 13 dlg_icp_params, 14 dlg_icp_stats, 15 dlg_icp_iteration, 17 dlg_fpfh_params, 18 dlg_fpfh_stats,
+ * 19 dlg_sac_ia_params, 20 dlg_sac_ia_hypothesis, 21 dlg_sac_ia_stats (12 and 16 are unassigned);
+ * -1 otherwise */
 int64_t dlg_abi_struct_size(int which);
 
 /* ---- contexts ------------------------------------------------------------------------------ */
@@ -691,6 +694,116 @@ dlg_status dlg_fpfh_estimate(dlg_ctx* ctx, const dlg_points* pts, const float* n
 dlg_status dlg_cloud_fpfh(dlg_ctx* ctx, dlg_cloud* cloud, const dlg_fpfh_params* params,
                           float* hist_out, int64_t hist_stride_bytes, int32_t* neighbours,
                           dlg_fpfh_stats* stats);
+
+/* ---- SAC-IA initial alignment (Dialog/PCLViewer.cpp:546-558, "registration" before ICP) ------- */
+/* pcl::SampleConsensusInitialAlignment<PointXYZ, PointXYZ, FPFHSignature33>::align(output, guess)
+ * of PCL 1.8 with the default TruncatedError, restated (from memory: parity unpinned, DESIGN.md
+ * section 2; csrc/sacia_model.hpp holds the arithmetic).
+ *   final = guess (NULL: identity).  A guess that is not approximately the identity -- in double
+ *   from the float entries, sum (g - I)^2 > (double)(0.01f * 0.01f) * min(sum g^2, 4) -- is scored
+ *   as iteration 0 and the drawn iterations start at 1.
+ *   One iteration, all of whose draws depend on the source coordinates alone:
+ *   1. selectSamples: getRandomIndex(n) = (int)(n * (rand() / (RAND_MAX + 1.0))) (double) until
+ *      nr_samples indices are accepted; a draw is rejected when it equals an accepted index or when
+ *      its float distance sqrtf((dx^2 + dy^2) + dz^2) to an accepted sample is < the call's copy of
+ *      min_sample_distance; 3 n consecutive rejections multiply that copy by 0.5f.
+ *   2. findSimilarFeatures: per sample, in order, the k_correspondences nearest valid target rows
+ *      of its descriptor in (d, index) order, d = FLANN's L2_Simple (r = 0; r += (a_j - b_j) *
+ *      (a_j - b_j), j = 0..32, float, no contraction); one getRandomIndex(k) picks the rank.
+ *   3. the rigid estimate of the nr_samples pairs: the exact integer moments of dlg_icp_align
+ *      (e = the exponent of the pairs' largest |coordinate|), Horn's closed form, t = ct - R cs,
+ *      cast to float.  PCL's float umeyama is not used.
+ *   4. the error: per source point moved through T (as dlg_icp_align moves one), e = the squared
+ *      distance to the nearest valid target point (ties cannot show), term = e <= thr ? e / thr :
+ *      1.0f with thr = (float)max_correspondence_distance (out of range: +inf; compared with the
+ *      SQUARED distance, as PCL does; a NaN term counts as 1.0f), E = sum trunc(term 2^48), an exact
+ *      integer: no visiting order, batch size or launch shape shows in any bit.  A source point that
+ *      is not finite before or after the transformation adds nothing.
+ *   5. the hypothesis is adopted when nothing has been scored yet or E is strictly below the lowest
+ *      E so far; adopting sets converged.
+ *   A target row is valid when its point and its 33 descriptor values are finite.  A draw that
+ *   lands on a source point or a source row that is not finite is still a draw, and the rank draws
+ *   are consumed; the hypothesis is invalid: not searched, not estimated, never adopted.
+ *   With PCL's default max_correspondence_distance thr is +inf, every E is 0 and the result is the
+ *   first valid hypothesis: the reference's own configuration (it sets no distance).
+ *   rand() is glibc's (rng 0) or the Visual C++ runtime's (rng 1), seeded with seed (PCL never
+ *   calls srand: 1).
+ * DLG_ERR_INVALID: nr_samples > n_src, a parameter outside its range, a bad stride, null features,
+ * a non-finite guess, a max_correspondence_distance that is NaN or <= 0, fewer than
+ * k_correspondences valid target rows, a context of a communicator with world > 1, a count above
+ * INT32_MAX. */
+typedef struct {
+  int32_t max_iterations;      /* setMaximumIterations (1000); >= 0 */
+  int32_t nr_samples;          /* setNumberOfSamples (3); 3..8 */
+  int32_t k_correspondences;   /* setCorrespondenceRandomness (10); 1..32 */
+  int32_t rng;                 /* 0 glibc rand(), 1 MSVC rand() */
+  uint32_t seed;               /* srand (1) */
+  int32_t compute_fitness;     /* != 0: stats->fitness = getFitnessScore(fitness_max_range) */
+  int32_t batch;               /* tests only: hypotheses per scoring launch (0: the library's choice) */
+  int32_t max_blocks;          /* tests only: n >= 1 = at most n workgroups per scoring launch */
+  float min_sample_distance;   /* setMinSampleDistance (0) */
+  double max_correspondence_distance; /* setMaxCorrespondenceDistance (sqrt(DBL_MAX)) */
+  double fitness_max_range;    /* getFitnessScore's max_range (DBL_MAX) */
+} dlg_sac_ia_params;           /* dlg_abi_struct_size(19) */
+
+typedef struct {
+  int32_t sample[8];           /* the source indices drawn (-1: unused slots, the scored guess) */
+  int32_t match[8];            /* the target rows picked (-1: unused, invalid) */
+  int32_t rank[8];             /* the ranks drawn (-1: unused) */
+  int32_t valid;               /* 0: a sample or its row was not finite */
+  int32_t relaxations;         /* halvings of min_sample_distance in this iteration */
+  int64_t draws;               /* rand() calls of this iteration */
+  float T[16];                 /* row-major; zero when invalid */
+  uint64_t err_hi, err_lo;     /* E = err_hi 2^24 + err_lo, err_lo < 2^24 */
+  int64_t n_far;               /* terms that were 1.0f */
+  int64_t n_used;              /* source points that added a term */
+} dlg_sac_ia_hypothesis;       /* dlg_abi_struct_size(20) */
+
+typedef struct {
+  int32_t iterations;          /* records: the scored guess and the drawn iterations */
+  int32_t converged;           /* hasConverged: a hypothesis was adopted */
+  int32_t best_iteration;      /* the adopted record (-1: none, final = guess) */
+  int32_t n_valid, n_invalid;  /* drawn hypotheses */
+  int32_t batches;             /* scoring batches */
+  int32_t levels;              /* hierarchy levels a pair of the call reached */
+  int32_t reserved;
+  int64_t draws, relaxations;  /* over every iteration */
+  int64_t n_queries;           /* distinct source descriptors searched */
+  int64_t host_syncs;          /* stream synchronisations after the target hierarchy's build */
+  double error;                /* RN(E) 2^-48 of the lowest scored hypothesis (0: none) */
+  double fitness;              /* compute_fitness != 0, else 0 */
+  double build_ms;             /* profiling: the target hierarchy's build (its read-backs included) */
+  double knn_ms, score_ms;     /* profiling: HIP events around the descriptor search, the scoring */
+  double device_ms;            /* their sum */
+} dlg_sac_ia_stats;            /* dlg_abi_struct_size(21) */
+
+void dlg_sac_ia_params_default(dlg_sac_ia_params* p);
+/* KdTreeFLANN<FPFHSignature33>::nearestKSearch by the kernel dlg_sac_ia_align runs: per query (33
+ * floats first in a record of q_stride_bytes) the k (1..32) nearest rows with 33 finite values, in
+ * (d, index) order: idx_out and d_out are n_queries x k.  A query with a non-finite value gets -1
+ * and 0.  DLG_ERR_INVALID when fewer than k rows are valid, a stride < 132 or no multiple of 4. */
+dlg_status dlg_fpfh_knn(dlg_ctx* ctx, const float* queries, int64_t q_stride_bytes,
+                        int64_t n_queries, const float* rows, int64_t row_stride_bytes,
+                        int64_t n_rows, int32_t k, int32_t* idx_out, float* d_out);
+/* computeErrorMetric of the caller's n_transforms row-major 4x4 transformations by the kernels
+ * dlg_sac_ia_align runs; every finite target point is valid.  hyp_out: one record each, of which
+ * T, err_hi, err_lo, n_far and n_used are filled (valid = 1, the rest as for a scored guess).
+ * batch, max_blocks: as in dlg_sac_ia_params. */
+dlg_status dlg_sac_ia_score(dlg_ctx* ctx, const dlg_points* src, const dlg_points* tgt,
+                            const float* transforms, int64_t n_transforms,
+                            double max_correspondence_distance, int32_t batch, int32_t max_blocks,
+                            dlg_sac_ia_hypothesis* hyp_out);
+/* src_features / tgt_features: one record of *_feat_stride bytes (>= 132, a multiple of 4) per
+ * point, 33 floats first.  guess (nullable), final_out, aligned_out (nullable; final applied to
+ * every source point) and out_stride_bytes as in dlg_icp_align.  hyp_out (nullable): the first
+ * hyp_cap records; the scored guess is record 0 with draws = 0 and sample = -1. */
+dlg_status dlg_sac_ia_align(dlg_ctx* ctx, const dlg_points* src, const float* src_features,
+                            int64_t src_feat_stride, const dlg_points* tgt,
+                            const float* tgt_features, int64_t tgt_feat_stride,
+                            const dlg_sac_ia_params* params, const float* guess, float* final_out,
+                            float* aligned_out, int64_t out_stride_bytes,
+                            dlg_sac_ia_hypothesis* hyp_out, int64_t hyp_cap,
+                            dlg_sac_ia_stats* stats);
 
 /* ---- postProcessPlanes (Dialog/PlaneDetect.h:1454-1579) ------------------------------------ */
 /* The final planes (plane_clouds_final, HeaderFile.h:98; struct Plane HeaderFile.h:81-88) as
