@@ -44,6 +44,7 @@ SYMBOLS = [
     "dlg_icp_params_default", "dlg_icp_align", "dlg_icp_correspondences", "dlg_cull_stats",
     "dlg_fpfh_estimate", "dlg_cloud_fpfh",
     "dlg_sac_ia_params_default", "dlg_fpfh_knn", "dlg_sac_ia_score", "dlg_sac_ia_align",
+    "dlg_debug_live_bytes",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -275,6 +276,8 @@ def load():
     L.dlg_barrier.argtypes = [vp]
     L.dlg_score_benchmark.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double,
                                       C.POINTER(C.c_double), i32p]
+    L.dlg_debug_live_bytes.restype = C.c_int64
+    L.dlg_debug_live_bytes.argtypes = [C.c_int]
     L.dlg_float_sums.argtypes = [vp, fp, C.c_int64, fp, C.c_int, fp, fp, C.POINTER(C.c_int),
                                  C.POINTER(C.c_double), i64p]
     L.dlg_ctx_set_option.argtypes = [vp, C.c_int, C.c_int64]
@@ -357,7 +360,7 @@ def load():
     for s in SYMBOLS:
         if s not in ("dlg_abi_version", "dlg_status_string", "dlg_sac_params_default",
                      "dlg_last_error", "dlg_abi_struct_size", "dlg_icp_params_default",
-                     "dlg_sac_ia_params_default"):
+                     "dlg_sac_ia_params_default", "dlg_debug_live_bytes"):
             getattr(L, s).restype = C.c_int
     _lib = L
     return L

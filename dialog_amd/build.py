@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdialog_amd.so")
-SOURCES = ["kernels.hip", "fsum.hip", "spatial.hip", "normals.hip", "postprocess.hip", "comm.cpp", "driver.cpp", "segment.cpp", "sac_control.cpp",
+SOURCES = ["kernels.hip", "fsum.hip", "spatial.hip", "normals.hip", "postprocess.hip", "comm.cpp", "cloud_call.cpp", "driver.cpp", "segment.cpp", "sac_control.cpp",
            "normals_host.cpp", "postprocess_host.cpp", "voxel.hip", "voxel_host.cpp",
            "sor.hip", "sor_host.cpp", "mls.hip", "mls_host.cpp", "icp.hip", "icp_host.cpp",
            "fpfh.hip", "fpfh_host.cpp", "sacia.hip", "sacia_host.cpp"]

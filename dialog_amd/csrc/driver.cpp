@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/dialog_ransac.h"
+#include "cloud_call.hpp"
 #include "comm.hpp"
 #include "driver.hpp"
 #include "fsum.hpp"  // (dlg_float_sums)
@@ -133,13 +134,6 @@ void dlg::finish_upload(dlg_ctx* c, dlg_cloud* cl, int64_t n) {
   std::memcpy(&cl->fmax, &bits[3], 4);
   if (c->opt.prune != 0 && n >= 3 && (n >= kPruneMinPoints || c->opt.prune == 1))
     build_spatial(c, cl);
-}
-
-void dlg::release_cloud_buffers(dlg_cloud* cl) {
-  cl->pristine.release();
-  cl->sp_pristine.release();
-  cl->sp_tiles_pr.release();
-  cl->sp_supers_pr.release();
 }
 
 // ================================================================================================
@@ -279,37 +273,6 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   c->comm.reset();
-  c->pos.release(); c->samples.release(); c->hyps.release(); c->res.release();
-  c->tile_in.release(); c->tile_off_in.release(); c->tile_off_out.release(); c->totals.release();
-  c->partials.release(); c->moments.release(); c->scratch_f64.release(); c->inl_gid.release(); c->inl_xyz.release();
-  c->small.release(); c->h_small.release(); c->sig.release();
-  c->gath64.release(); c->gath32.release();
-  c->h_pos.release(); c->h_res.release(); c->h_tot.release(); c->h_mom.release(); c->h_g64.release();
-  c->h_stage.release();
-  c->pick.release(); c->h_pick.release(); c->rk.release(); c->h_rk.release();
-  if (c->pub) (void)hipHostFree(c->pub);
-  c->pub = nullptr;
-  c->pub_cap = 0;
-  c->nw.release();
-  c->pw.release();
-  c->vw.release();
-  c->sw.release();
-  c->mw.release();
-  c->iw.release();
-  c->fw.release();
-  c->aw.release();
-  c->pstats.release();
-  c->cull_i.release();
-  c->cull_h.release();
-  c->sel1_status.release();
-  c->sel1_err.release();
-  c->sel1_tk.release();
-  c->lp.release();
-  c->lp_n.release();
-  c->fs_scr.release();
-  c->fs_x.release(); c->fs_y.release(); c->fs_z.release(); c->fs_n.release();
-  c->mk0.release(); c->mk1.release(); c->mi0.release(); c->mi1.release(); c->msort.release(); c->mxyz.release();
-  c->mom_done.release(); c->pick_done.release();
   if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
   if (c->ev_inl) (void)hipEventDestroy(c->ev_inl);
   if (c->cstream) {
@@ -331,9 +294,11 @@ dlg_status dlg_ctx_destroy(dlg_ctx* c) {
   for (auto& ev : c->ev)
     if (ev) (void)hipEventDestroy(ev);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // (frees every buffer the context owns)
   return DLG_OK;
 }
+
+int64_t dlg_debug_live_bytes(int pinned) { return g_live_bytes[pinned ? 1 : 0].load(); }
 
 const char* dlg_last_error(const dlg_ctx* c) {
   return c ? c->err.c_str() : g_last_create_error.c_str();
@@ -349,39 +314,19 @@ dlg_status dlg_ctx_info(const dlg_ctx* c, int* rank, int* world, int* device) {
 
 dlg_status dlg_cloud_upload(dlg_ctx* c, const dlg_points* pts, const int32_t* indices,
                             int64_t n_indices, int32_t id_base, dlg_cloud** out) {
-  if (!c || !pts || !out || (pts->n > 0 && !pts->xyz) || pts->n < 0) return DLG_ERR_INVALID;
-  if (pts->stride_bytes < 12 || pts->stride_bytes % 4) return fail(c, DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
-  if (indices && n_indices < 0) return fail(c, DLG_ERR_INVALID, "negative n_indices");
-  *out = nullptr;
-  auto cl = std::make_unique<dlg_cloud>();
-  dlg_status s = guarded(c, [&] {
-    const int64_t n = indices ? n_indices : pts->n;
-    if (n > INT32_MAX) throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 points");
+  if (!c || !out) return DLG_ERR_INVALID;
+  return make_cloud(c, id_base, out, [&](dlg_cloud& cl) {
+    check_points(pts, "points", indices ? INT64_MAX : kMaxPoints);  // (a list may pick from more)
+    const int64_t n = check_list(indices, n_indices, pts->n);
     const int64_t sf = pts->stride_bytes / 4;
-    cl->ctx = c;
-    cl->n_total = n;
-    cl->n_points = pts->n;
-    cl->id_base = id_base;
-    cl->gid_ident = indices == nullptr;
-    cl->n_active = n;
-    cl->pristine.ensure((size_t)std::max<int64_t>(n, 1));
-    if (indices)
-      for (int64_t i = 0; i < n; ++i)
-        if (indices[i] < 0 || indices[i] >= pts->n) throw DlgError(DLG_ERR_INVALID, "index out of range");
+    SoA& rows = cloud_rows(cl, n);
+    cl.n_points = pts->n;
+    cl.gid_ident = indices == nullptr;
     if (n && (!indices || 4 * n >= pts->n)) {
       // the caller's records go up as they are (one DMA), the SoA split and ids on the device
-      DevBuf<uint8_t>& raw = c->nw.raw;
-      const size_t bytes = (size_t)pts->n * (size_t)pts->stride_bytes;
-      raw.ensure(bytes + (indices ? 4 * (size_t)n : 0));
-      HIPCHK(hipMemcpyAsync(raw.p, pts->xyz, bytes, hipMemcpyHostToDevice, c->stream));
-      const int32_t* didx = nullptr;
-      if (indices) {
-        HIPCHK(hipMemcpyAsync(raw.p + bytes, indices, 4 * (size_t)n, hipMemcpyHostToDevice,
-                              c->stream));
-        didx = reinterpret_cast<const int32_t*>(raw.p + bytes);
-      }
-      launch_upload_gather(reinterpret_cast<const float*>(raw.p), sf, didx, n, id_base,
-                           cl->pristine.out(), c->stream);
+      const float* raw = upload_raw(c, pts);
+      launch_upload_gather(raw, sf, stage_list(c, indices, (int)n), n, id_base, rows.out(),
+                           c->stream);
       HIPCHK(hipGetLastError());
     } else if (n) {
       // a small subset of a large cloud: gather on the host
@@ -393,43 +338,21 @@ dlg_status dlg_cloud_upload(dlg_ctx* c, const dlg_points* pts, const int32_t* in
         x[i] = p[0]; y[i] = p[1]; z[i] = p[2];
         g[i] = (int32_t)(id_base + k);
       }
-      HIPCHK(hipMemcpyAsync(cl->pristine.x.p, x.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(cl->pristine.y.p, y.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(cl->pristine.z.p, z.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(cl->pristine.gid.p, g.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(rows.x.p, x.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(rows.y.p, y.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(rows.z.p, z.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(rows.gid.p, g.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
       sync(c);  // the host vectors go out of scope
     }
-    finish_upload(c, cl.get(), n);
+    return n;
   });
-  if (s != DLG_OK) {
-    release_cloud_buffers(cl.get());
-    return s;
-  }
-  *out = cl.release();
-  return DLG_OK;
 }
 
 dlg_status dlg_cloud_destroy(dlg_cloud* cl) {
   if (!cl) return DLG_OK;
   if (cl->ctx) (void)hipSetDevice(cl->ctx->device);
   if (cl->ctx && cl->ctx->stream) (void)hipStreamSynchronize(cl->ctx->stream);
-  cl->pristine.release();
-  cl->raw_nrm.release();
-  cl->buf[0].release();
-  cl->buf[1].release();
-  cl->sp_pristine.release();
-  cl->sp_buf[0].release();
-  cl->sp_buf[1].release();
-  cl->sp_tiles_pr.release();
-  cl->sp_supers_pr.release();
-  cl->sp_order.release();
-  for (int b = 0; b < 2; ++b) {
-    cl->sp_tb[b].release();
-    cl->sp_sb[b].release();
-  }
-  cl->ubits.release();
-  cl->tag.release();
-  delete cl;
+  delete cl;  // (frees every buffer the cloud owns)
   return DLG_OK;
 }
 

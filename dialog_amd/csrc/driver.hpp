@@ -1,29 +1,29 @@
-// driver.hpp -- host-side state shared by the RANSAC driver (driver.cpp, segment.cpp) and the normals driver
-// (normals_host.cpp): error type, device/pinned buffers, the context and cloud objects.
+// driver.hpp -- host-side state shared by every host driver (the RANSAC rounds in driver.cpp and
+// segment.cpp, the normals path, postProcessPlanes and the six cloud filters / registration calls):
+// the owning device and pinned buffers, each driver's scratch, the context and cloud objects.
+// (The error type and the argument checks: call_args.hpp.)
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dialog_ransac.h"
+#include "call_args.hpp"
 #include "comm.hpp"
 #include "kernels.hpp"
 #include "sac_control.hpp"
 #include "postprocess.hpp"
 
 namespace dlg {
-
-struct DlgError : std::runtime_error {
-  DlgError(dlg_status c, const std::string& m) : std::runtime_error(m), code(c) {}
-  dlg_status code;
-};
 
 #define HIPCHK(expr)                                                                          \
   do {                                                                                        \
@@ -32,45 +32,82 @@ struct DlgError : std::runtime_error {
       throw DlgError(DLG_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_));       \
   } while (0)
 
+// bytes this process holds in DevBuf ([0]) and PinBuf ([1]) allocations (dlg_debug_live_bytes)
+inline std::atomic<int64_t> g_live_bytes[2];
+
+// Device memory of one owner: grown by ensure() (never shrunk, contents not kept), freed by
+// release() or the destructor.  The device it was allocated on must be current when it dies
+// (dlg_ctx_destroy, dlg_cloud_destroy and a failed cloud call see to that).
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   void ensure(size_t n) {
     if (n <= cap) return;
     if (p) HIPCHK(hipFree(p));
-    p = nullptr;
-    cap = 0;
+    forget();
     size_t want = std::max<size_t>(n, 16);
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T)));
     cap = want;
+    g_live_bytes[0] += (int64_t)(cap * sizeof(T));
   }
   void release() {
     if (p) (void)hipFree(p);
+    forget();
+  }
+
+ private:
+  void forget() {
+    g_live_bytes[0] -= (int64_t)(cap * sizeof(T));
     p = nullptr;
     cap = 0;
   }
 };
 
-template <typename T>
+// pinned host memory, the same way (Flags: hipHostMallocCoherent for what a kernel publishes)
+template <typename T, unsigned Flags = hipHostMallocDefault>
 struct PinBuf {
   T* p = nullptr;
   size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { release(); }
   void ensure(size_t n) {
     if (n <= cap) return;
     if (p) HIPCHK(hipHostFree(p));
-    p = nullptr;
-    cap = 0;
+    forget();
     size_t want = std::max<size_t>(n, 16);
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p), want * sizeof(T), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p), want * sizeof(T), Flags));
     cap = want;
+    g_live_bytes[1] += (int64_t)(cap * sizeof(T));
   }
   void release() {
     if (p) (void)hipHostFree(p);
+    forget();
+  }
+
+ private:
+  void forget() {
+    g_live_bytes[1] -= (int64_t)(cap * sizeof(T));
     p = nullptr;
     cap = 0;
   }
 };
+
+// (an owner is never copied or moved: the aggregates below are built in place)
+static_assert(!std::is_copy_constructible<DevBuf<float>>::value &&
+                  !std::is_copy_assignable<DevBuf<float>>::value &&
+                  !std::is_move_constructible<DevBuf<float>>::value,
+              "DevBuf owns its allocation");
+static_assert(!std::is_copy_constructible<PinBuf<float>>::value &&
+                  !std::is_copy_assignable<PinBuf<float>>::value &&
+                  !std::is_move_constructible<PinBuf<float>>::value,
+              "PinBuf owns its allocation");
 
 struct SoA {
   DevBuf<float> x, y, z;
@@ -79,7 +116,6 @@ struct SoA {
   bool with_nrm = false;
   void ensure(size_t n) { x.ensure(n); y.ensure(n); z.ensure(n); gid.ensure(n); }
   void ensure_nrm(size_t n) { nrm.ensure(n); with_nrm = true; }
-  void release() { x.release(); y.release(); z.release(); gid.release(); nrm.release(); with_nrm = false; }
   PointsView view(int64_t n) const {
     return PointsView{x.p, y.p, z.p, gid.p, n, with_nrm ? nrm.p : nullptr};
   }
@@ -92,13 +128,11 @@ struct GridLevelBufs {
   DevBuf<int32_t> idx, pos;
   DevBuf<uint32_t> tkeys;
   DevBuf<int2> trange;
-  void release() {
-    sx.release(); sy.release(); sz.release(); idx.release(); pos.release(); tkeys.release();
-    trange.release();
-  }
 };
 
-// scratch of the normals / RegulateNormal path (normals_host.cpp)
+// scratch of the normals / RegulateNormal path (normals_host.cpp), and what the cloud calls share
+// (cloud_call.cpp): the raw upload, the staged index list, the de-interleaved cloud with its flags
+// and kept positions, the kept points and their grids
 struct NormalsWork {
   static constexpr int kLevels = 12;
   GridLevelBufs lv[kLevels];
@@ -119,20 +153,10 @@ struct NormalsWork {
   PinBuf<long long> h_bst;
   DevBuf<unsigned long long> keys64, keys_alt;
   PinBuf<uint32_t> h_cnt;
-  void release() {
-    for (auto& l : lv) l.release();
-    raw.release(); out.release(); processed.release(); processed_s.release(); sort_tmp.release(); dflags.release();
-    fs_scr.release();
-    x.release(); y.release(); z.release(); qx.release(); qy.release(); qz.release();
-    partial.release(); nn.release();
-    keys_in.release(); keys_out.release(); counters.release();
-    idx_in.release(); queue.release(); cand.release(); ids.release(); ids_alt.release();
-    pos_of.release(); nrm.release(); nrm_s.release(); claim.release(); keys64.release();
-    keys_alt.release(); h_cnt.release(); ccnt.release(); coffs.release(); ccur.release(); cdone.release();
-    sd2.release(); bst.release(); h_bst.release(); ctile.release(); cslot.release();
-    ncnt.release(); noff.release(); nkeys.release();
-    ovfa.release(); ovfb.release(); ovfc.release(); rec.release();
-  }
+  DevBuf<int32_t> lst;         // a call's index list (stage_list)
+  DevBuf<float> ax, ay, az;    // flag_points: the uploaded cloud de-interleaved, original order
+  DevBuf<uint8_t> flags;       //   its flagged rows
+  DevBuf<int32_t> fin_pos;     //   their positions, ascending
 };
 
 // scratch of postProcessPlanes (postprocess_host.cpp)
@@ -144,103 +168,63 @@ struct PostWork {
   DevBuf<float4> planes, rays;
   DevBuf<PipEdge> edges;
   DevBuf<int64_t> edge_off;
-  void release() {
-    processed.release(); flags.release(); absorbed.release(); keep.release();
-    bcnt.release(); boff.release(); offs.release(); abs_cnt.release(); mask.release();
-    csize.release(); cand.release(); cand2.release(); ids.release(); parent.release(); sel.release();
-    rids.release(); out.release(); table.release(); rest.release(); tasks.release(); planes.release(); rays.release();
-    edges.release(); edge_off.release();
-  }
 };
 
 // scratch of the voxel-grid filter (voxel_host.cpp; the list-order coordinates and records, the raw
-// upload and the hipcub temporaries are the normals path's nw.x/y/z, nw.rec, nw.raw, nw.sort_tmp)
+// upload, the staged list and the hipcub temporaries are the shared nw.x/y/z, nw.rec, nw.raw,
+// nw.lst, nw.sort_tmp)
 struct VoxelWork {
   DevBuf<uint8_t> flags, lflag;
   DevBuf<uint32_t> keys_in, keys_out;
   DevBuf<int32_t> fin_pos, pos_in, pos_out, head, vid, vstart, keep, row, long_list, ocnt, voe;
   DevBuf<float> sx, sy, sz, ox, oy, oz;
-  void release() {
-    flags.release(); lflag.release(); keys_in.release(); keys_out.release(); fin_pos.release();
-    pos_in.release(); pos_out.release(); head.release(); vid.release(); vstart.release();
-    keep.release(); row.release(); long_list.release(); ocnt.release(); voe.release();
-    sx.release(); sy.release(); sz.release(); ox.release(); oy.release(); oz.release();
-  }
 };
 
-// scratch of the statistical outlier filter (sor_host.cpp; the finite points and the hierarchy are
-// the normals path's nw.x/y/z and nw.lv[])
+// scratch of the statistical outlier filter (sor_host.cpp; the cloud, its finite points and their
+// hierarchy are the shared nw.ax/ay/az, nw.x/y/z and nw.lv[])
 struct SorWork {
-  DevBuf<uint8_t> flags, need, keep, rem;
-  DevBuf<float> ax, ay, az, dist_pt, dist;
-  DevBuf<int32_t> fin_pos, rank, sel_keep, sel_rem, out_keep, out_rem;
+  DevBuf<uint8_t> need, keep, rem;
+  DevBuf<float> dist_pt, dist;
+  DevBuf<int32_t> rank, sel_keep, sel_rem, out_keep, out_rem;
   DevBuf<unsigned long long> acc;
-  void release() {
-    flags.release(); need.release(); keep.release(); rem.release();
-    ax.release(); ay.release(); az.release(); dist_pt.release(); dist.release();
-    fin_pos.release(); rank.release(); sel_keep.release(); sel_rem.release();
-    out_keep.release(); out_rem.release(); acc.release();
-  }
 };
 
-// scratch of the moving-least-squares filter (mls_host.cpp; the points and the grid are the normals
-// path's nw.x/y/z and nw.lv[0])
+// scratch of the moving-least-squares filter (mls_host.cpp; the points, the grid and the staged
+// list are the shared nw.x/y/z, nw.lv[0] and nw.lst)
 struct MlsWork {
   DevBuf<uint8_t> need, valid;
   DevBuf<float4> res_p, res_n, o_nrm;  // per point: (x, y, z, branch), (nx, ny, nz, curvature)
-  DevBuf<int32_t> lst, cnt, sel, o_src, o_nb;
+  DevBuf<int32_t> cnt, sel, o_src, o_nb;
   DevBuf<float> o_xyz;
   DevBuf<unsigned long long> acc;
-  void release() {
-    need.release(); valid.release(); res_p.release(); res_n.release(); o_nrm.release();
-    lst.release(); cnt.release(); sel.release(); o_src.release(); o_nb.release(); o_xyz.release(); acc.release();
-  }
 };
 
-// scratch of the FPFH descriptors (fpfh_host.cpp; the points and the grid are the normals path's
-// nw.x/y/z and nw.lv[0], the normals nw.nrm)
+// scratch of the FPFH descriptors (fpfh_host.cpp; the points, the grid and the staged list are the
+// shared nw.x/y/z, nw.lv[0] and nw.lst, the normals nw.nrm)
 struct FpfhWork {
   DevBuf<float4> snrm;             // the normals in the grid's sorted order
   DevBuf<float> spfh, hist;        // n x 33 SPFH table; one 33-float row per list entry
-  DevBuf<int32_t> lst, cnt, pairs, counts, o_nb;
+  DevBuf<int32_t> cnt, pairs, counts, o_nb;
   DevBuf<unsigned long long> acc;
-  void release() {
-    snrm.release(); spfh.release(); hist.release(); lst.release(); cnt.release(); pairs.release();
-    counts.release(); o_nb.release(); acc.release();
-  }
 };
 
-// scratch of the rigid registration (icp_host.cpp; the finite target points and their hierarchy are
-// the normals path's nw.x/y/z and nw.lv[])
+// scratch of the rigid registration (icp_host.cpp; the target, its finite points and their
+// hierarchy are the shared nw.ax/ay/az, nw.x/y/z and nw.lv[])
 struct IcpWork {
-  DevBuf<uint8_t> flags, state;      // (state: one IcpState, icp.hpp)
-  DevBuf<float> tx, ty, tz, wx, wy, wz, d2;
-  DevBuf<int32_t> fin_pos, qa, qb, nn;
-  void* pub = nullptr;  // coherent pinned: k_icp_publish's copy of the state
-  void release() {
-    flags.release(); state.release(); tx.release(); ty.release(); tz.release();
-    wx.release(); wy.release(); wz.release(); d2.release();
-    fin_pos.release(); qa.release(); qb.release(); nn.release();
-    if (pub) (void)hipHostFree(pub);
-    pub = nullptr;
-  }
+  DevBuf<uint8_t> state;             // one IcpState (icp.hpp)
+  DevBuf<float> wx, wy, wz, d2;
+  DevBuf<int32_t> qa, qb, nn;
+  PinBuf<uint8_t, hipHostMallocCoherent> pub;  // k_icp_publish's copy of the state
 };
 
-// scratch of the SAC-IA initial alignment (sacia_host.cpp; the valid target points and their
-// hierarchy are the normals path's nw.x/y/z and nw.lv[])
+// scratch of the SAC-IA initial alignment (sacia_host.cpp; the target, its valid rows and points
+// and their hierarchy are the shared nw.ax/ay/az, nw.flags, nw.x/y/z and nw.lv[])
 struct SaciaWork {
-  DevBuf<uint8_t> flags, pflags, state;  // valid rows; valid points; one SaciaState (sacia.hpp)
-  DevBuf<float> tx, ty, tz, sx, sy, sz;  // the target's and the source's points, de-interleaved
+  DevBuf<uint8_t> state;             // one SaciaState (sacia.hpp)
+  DevBuf<float> sx, sy, sz;          // the source's points, de-interleaved
   DevBuf<float> rows, queries, part_d, knn_d, xfs;
-  DevBuf<int32_t> fin_pos, part_i, knn_i;
+  DevBuf<int32_t> part_i, knn_i;
   DevBuf<unsigned long long> qa, qb, acc;
-  void release() {
-    flags.release(); pflags.release(); state.release();
-    tx.release(); ty.release(); tz.release(); sx.release(); sy.release(); sz.release();
-    rows.release(); queries.release(); part_d.release(); knn_d.release(); xfs.release();
-    fin_pos.release(); part_i.release(); knn_i.release();
-    qa.release(); qb.release(); acc.release();
-  }
 };
 
 }  // namespace dlg
@@ -376,8 +360,7 @@ struct dlg_ctx {
   hipEvent_t ev_score_end = nullptr;  // (profiling) the last speculative round's scoring end
   bool stage_inflight = false;
   DevBuf<int32_t> pick;   // k_pick_p1 result
-  int32_t* pub = nullptr;  // coherent pinned: k_publish's round results (pub[0] = sequence)
-  size_t pub_cap = 0;
+  PinBuf<int32_t, hipHostMallocCoherent> pub;  // k_publish's round results (pub[0] = sequence)
   int32_t pub_seq = 0;
   // the last compaction's predicted Morton-copy totals, checked at the next publish
   bool sp_check = false;
@@ -523,11 +506,10 @@ dlg_status guarded_group(dlg_ctx* c, F&& f) {
   return s;
 }
 
-// the tail of an upload, shared by dlg_cloud_upload and dlg_voxel_grid_cloud: the cloud's n points
-// and ids are in its pristine list on the device; computes amax / fmax and builds the spatial copy
-// under DLG_OPT_PRUNE's rule.  release_cloud_buffers: what a failed upload frees before the delete.
+// the tail of an upload (make_cloud, cloud_call.hpp): the cloud's n points and ids are in its
+// pristine list on the device; computes amax / fmax and builds the spatial copy under
+// DLG_OPT_PRUNE's rule
 void finish_upload(dlg_ctx* c, dlg_cloud* cl, int64_t n);
-void release_cloud_buffers(dlg_cloud* cl);
 
 // normals on the device -> the cloud (dlg_cloud_set_normals, dlg_cloud_estimate_normals)
 void attach_normals(dlg_ctx* c, dlg_cloud* cl, const float* raw_dev, int64_t stride_f,

@@ -15,7 +15,7 @@ namespace dlg {
 // entry with more neighbours takes them in several sorted windows, each a scan of the grid
 constexpr int kFpfhCap = 1024;
 
-// acc[] of a call (zeroed by the caller; [0] is launch_mls_count_finite's)
+// acc[] of a call (zeroed by the caller)
 enum {
   kFpfhFinite = 0,       // finite points of the cloud
   kFpfhNanRows = 1,      // list entries with a non-finite coordinate

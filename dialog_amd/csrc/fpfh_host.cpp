@@ -10,38 +10,26 @@
 // each), then for the copy out.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 
-#include "driver.hpp"
+#include "cloud_call.hpp"
 #include "fpfh.hpp"
 #include "grid_host.hpp"
-#include "mls.hpp"  // launch_mls_count_finite
 #include "normals.hpp"
 #include "segment.hpp"  // event_ms
 
 namespace dlg {
 namespace {
 
-static_assert(kFpfhFinite == kMlsFinite, "launch_mls_count_finite counts into acc[kFpfhFinite]");
-
-void check_call(dlg_ctx* c, const dlg_fpfh_params* prm, int64_t n, const int32_t* indices,
-                int64_t n_indices, int64_t hist_stride) {
-  if (c->comm->world() > 1)
-    throw DlgError(DLG_ERR_INVALID, "FPFH: the points are one rank's shard (world > 1); the "
-                                    "neighbours across the cut need the whole cloud");
+// (the checks of both entry points but the points' and the list's)
+void check_call(dlg_ctx* c, const dlg_fpfh_params* prm, int64_t hist_stride) {
+  check_whole_cloud(c->comm->world(), "FPFH");
   if (!std::isfinite(prm->search_radius) || !(prm->search_radius > 0.0f))
     throw DlgError(DLG_ERR_INVALID, "search_radius must be finite and > 0");
   if (hist_stride < 4 * kFpfhDim || hist_stride % 4)
     throw DlgError(DLG_ERR_INVALID, "hist_stride_bytes must be >= 132 and a multiple of 4");
-  if (indices && n_indices < 0) throw DlgError(DLG_ERR_INVALID, "negative n_indices");
-  if (n > INT32_MAX || (indices && n_indices > INT32_MAX))
-    throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 points");
-  if (indices)
-    for (int64_t i = 0; i < n_indices; ++i)
-      if (indices[i] < 0 || indices[i] >= n) throw DlgError(DLG_ERR_INVALID, "index out of range");
 }
 
 // the points in nw.x/y/z (bounding box b), the normals in nw.nrm; everything from the grid build to
@@ -54,36 +42,31 @@ void fpfh_core(dlg_ctx* c, int n, const BBox& b, const int32_t* indices, int m,
   unsigned long long acc[kFpfhAccWords] = {};
   v.acc.ensure(kFpfhAccWords);
   HIPCHK(hipMemsetAsync(v.acc.p, 0, 8 * (size_t)kFpfhAccWords, c->stream));
-  launch_mls_count_finite(w.x.p, w.y.p, w.z.p, n, v.acc.p, c->stream);
+  launch_count_finite(w.x.p, w.y.p, w.z.p, n, v.acc.p + kFpfhFinite, c->stream);
   const bool run = n > 0 && m > 0;
   if (run) {
     if (!hist_out) throw DlgError(DLG_ERR_INVALID, "hist_out is null");
-    const int32_t* didx = nullptr;
-    if (indices) {
-      v.lst.ensure(m);
-      HIPCHK(hipMemcpyAsync(v.lst.p, indices, 4 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-      didx = v.lst.p;
-    }
+    const int32_t* didx = stage_list(c, indices, m);
     const size_t table = (size_t)n * kFpfhDim;
     v.snrm.ensure(n); v.spfh.ensure(table); v.cnt.ensure(n); v.pairs.ensure(n);
     v.hist.ensure((size_t)m * kFpfhDim); v.o_nb.ensure(m);
     if (spfh_counts) v.counts.ensure(table);
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    mark(c, 0);
     GridBufs B;
     const GridDesc G = make_grid(b, (double)prm->search_radius);
     build_grid(c, n, G, 0, &B);  // (synchronises)
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    mark(c, 1);
     const double r = (double)prm->search_radius;
     const float r2 = (float)(r * r);  // KdTreeFLANN: radius * radius
     launch_fpfh_sort_normals(B, n, w.nrm.p, v.snrm.p, c->stream);
     if (spfh_counts) HIPCHK(hipMemsetAsync(v.counts.p, 0, 4 * table, c->stream));
     launch_fpfh_spfh(G, B, n, r2, v.snrm.p, v.spfh.p, spfh_counts ? v.counts.p : nullptr, v.cnt.p,
                      v.pairs.p, c->num_cus, c->stream);
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[2], c->stream));
+    mark(c, 2);
     launch_fpfh_weight(G, B, n, r2, didx, m, w.x.p, w.y.p, w.z.p, v.spfh.p, v.pairs.p,
                        v.hist.p, v.o_nb.p, v.acc.p, c->num_cus, c->stream);
     HIPCHK(hipGetLastError());
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[3], c->stream));
+    mark(c, 3);
     HIPCHK(hipMemcpy2DAsync(hist_out, (size_t)hist_stride, v.hist.p, 4 * (size_t)kFpfhDim,
                             4 * (size_t)kFpfhDim, (size_t)m, hipMemcpyDeviceToHost, c->stream));
     if (neighbours)
@@ -123,16 +106,13 @@ dlg_status dlg_fpfh_estimate(dlg_ctx* c, const dlg_points* pts, const float* nor
   if (!c || !prm) return DLG_ERR_INVALID;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   return guarded(c, [&] {
-    if (!pts || pts->n < 0 || (pts->n > 0 && !pts->xyz))
-      throw DlgError(DLG_ERR_INVALID, "points: null or negative size");
-    if (pts->stride_bytes < 12 || pts->stride_bytes % 4)
-      throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
+    check_points(pts);
     if (!normals) throw DlgError(DLG_ERR_INVALID, "normals is null");
     if (normals_stride_bytes < 12 || normals_stride_bytes % 4)
       throw DlgError(DLG_ERR_INVALID, "normals_stride_bytes must be >= 12 and a multiple of 4");
-    check_call(c, prm, pts->n, indices, n_indices, hist_stride_bytes);
+    check_call(c, prm, hist_stride_bytes);
     const int n = (int)pts->n;
-    const int m = (int)(indices ? n_indices : pts->n);
+    const int m = check_list(indices, n_indices, n);
     NormalsWork& w = c->nw;
     BBox b = {};
     if (n > 0) {
@@ -155,7 +135,7 @@ dlg_status dlg_cloud_fpfh(dlg_ctx* c, dlg_cloud* cl, const dlg_fpfh_params* prm,
   if (stats) std::memset(stats, 0, sizeof(*stats));
   return guarded(c, [&] {
     if (!cl->has_normals) throw DlgError(DLG_ERR_INVALID, "the cloud has no normals attached");
-    check_call(c, prm, cl->n_total, nullptr, 0, hist_stride_bytes);
+    check_call(c, prm, hist_stride_bytes);
     const int n = (int)cl->n_total;
     NormalsWork& w = c->nw;
     BBox b = {};

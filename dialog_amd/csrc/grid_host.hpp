@@ -32,6 +32,5 @@ struct KnnPlan {
 void build_level(dlg_ctx* c, const KnnPlan& P, KnnLevels& L, int l, const GridBufs* B0);
 KnnLevels build_hierarchy_plan(dlg_ctx* c, int n, const BBox& b, int k_nn, KnnPlan* plan,
                                int eager_levels);
-void check_points(const dlg_points* pts);
 
 }  // namespace dlg

@@ -2,24 +2,22 @@
 // (include/dialog_ransac.h; pcl::IterativeClosestPoint<PointXYZ, PointXYZ> as
 // Dialog/PCLViewer.cpp:581-636 calls it).
 //
-// Once per call: the target's finite points are compacted into the normals path's nw.x/y/z and
-// their whole grid hierarchy is built; the listed source points become the working cloud W, which
-// stays on the device.  Per iteration: the level passes (the previous iteration's transformation
-// applied at level 0, deferrals counted on the device), the moments pass and the publish kernel,
-// then ONE stream synchronisation; the host runs the solve and the criteria (icp_model.hpp) and
-// the next level-0 pass takes the 16 floats as its argument.
+// Once per call: the target's finite points are compacted into the shared nw.x/y/z and their whole
+// grid hierarchy is built (build_target, cloud_call.hpp); the listed source points become the
+// working cloud W, which stays on the device.  Per iteration: the level passes (the previous
+// iteration's transformation applied at level 0, deferrals counted on the device), the moments pass
+// and the publish kernel, then ONE stream synchronisation; the host runs the solve and the criteria
+// (icp_model.hpp) and the next level-0 pass takes the 16 floats as its argument.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <string>
 
-#include "driver.hpp"
+#include "cloud_call.hpp"
 #include "grid_host.hpp"
 #include "icp.hpp"
 #include "normals.hpp"
@@ -27,14 +25,6 @@
 
 namespace dlg {
 namespace {
-
-void check_cloud(const dlg_points* p, const char* what) {
-  if (!p || p->n < 0 || (p->n > 0 && !p->xyz))
-    throw DlgError(DLG_ERR_INVALID, std::string(what) + ": null or negative size");
-  if (p->stride_bytes < 12 || p->stride_bytes % 4)
-    throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
-  if (p->n > INT32_MAX) throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 points");
-}
 
 // max_dist^2 as the pairs are tested against it
 double squared_limit(double max_dist) {
@@ -47,119 +37,73 @@ double squared_limit(double max_dist) {
 struct IcpCall {
   dlg_ctx* c;
   int m = 0;    // list entries = W's size
-  int nf = 0;   // finite target points
   int64_t n_src_finite = 0;
-  float tmax = 0.0f;  // the target's largest finite |coordinate|
-  KnnLevels L{};
+  float guess[16];  // the checked guess (the identity when none is given)
+  Target T;         // the finite target points and their hierarchy
   IcpState* st = nullptr;
   IcpState* pub = nullptr;
   int levels_used = 0;
   int64_t syncs = 0;
-  double build_ms = 0.0;
 
   explicit IcpCall(dlg_ctx* ctx) : c(ctx) {}
 
   // the target's hierarchy and W (moved by xf when given); ev[0] is recorded behind the build
   void setup(const dlg_points* src, const int32_t* indices, int64_t n_indices,
              const dlg_points* tgt, const float* xf16) {
-    if (c->comm->world() > 1)
-      throw DlgError(DLG_ERR_INVALID, "registration: the target is one rank's shard (world > 1); "
-                                      "the neighbours beyond its cut need the whole cloud");
-    check_cloud(src, "source");
-    check_cloud(tgt, "target");
-    if (indices && n_indices < 0) throw DlgError(DLG_ERR_INVALID, "negative n_indices");
-    if (indices && n_indices > INT32_MAX) throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 indices");
-    m = (int)(indices ? n_indices : src->n);
+    check_whole_cloud(c->comm->world(), "registration");
+    check_points(src, "source");
+    check_points(tgt, "target");
+    m = check_list(indices, n_indices, src->n);
     const int64_t sf = src->stride_bytes / 4;
     for (int i = 0; i < m; ++i) {
-      const int64_t j = indices ? indices[i] : i;
-      if (j < 0 || j >= src->n) throw DlgError(DLG_ERR_INVALID, "index out of range");
-      const float* p = src->xyz + j * sf;
+      const float* p = src->xyz + (indices ? indices[i] : i) * sf;
       n_src_finite += std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
     }
+    check_guess(xf16, guess);
     IcpXf xf{};
-    int apply = 0;
-    if (xf16) {
-      for (int k = 0; k < 16; ++k)
-        if (!std::isfinite(xf16[k])) throw DlgError(DLG_ERR_INVALID, "the guess is not finite");
-      std::memcpy(xf.m, xf16, 64);
-      apply = !icp_is_identity(xf16);
-    }
-    if (tgt->n == 0) throw DlgError(DLG_ERR_INVALID, "the target has no finite point");
-    NormalsWork& w = c->nw;
+    std::memcpy(xf.m, guess, 64);
+    const int apply = !icp_is_identity(guess);
     IcpWork& v = c->iw;
-    const auto t0 = std::chrono::steady_clock::now();
-    // 1. the target: upload, de-interleave, the finite points, their hierarchy (every level)
-    const int nt = (int)tgt->n;
-    const size_t tbytes = (size_t)nt * (size_t)tgt->stride_bytes;
-    w.raw.ensure(tbytes);
-    HIPCHK(hipMemcpyAsync(w.raw.p, tgt->xyz, tbytes, hipMemcpyHostToDevice, c->stream));
-    v.tx.ensure(nt); v.ty.ensure(nt); v.tz.ensure(nt);
-    v.flags.ensure(nt); v.fin_pos.ensure(nt);
-    launch_deinterleave(reinterpret_cast<const float*>(w.raw.p), nt, tgt->stride_bytes / 4, v.tx.p,
-                        v.ty.p, v.tz.p, c->stream);
-    launch_finite_flags(v.tx.p, v.ty.p, v.tz.p, nt, v.flags.p, c->stream);
-    w.sort_tmp.ensure(select_tmp_bytes(nt));
-    w.counters.ensure(8);
-    w.h_cnt.ensure(8);
-    HIPCHK(select_flagged(w.sort_tmp.p, w.sort_tmp.cap, v.flags.p, nt, v.fin_pos.p, w.counters.p,
-                          c->stream));
-    HIPCHK(hipMemcpyAsync(w.h_cnt.p, w.counters.p, 4, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    nf = (int)w.h_cnt.p[0];
-    if (nf == 0) throw DlgError(DLG_ERR_INVALID, "the target has no finite point");
-    w.x.ensure(nf); w.y.ensure(nf); w.z.ensure(nf);
-    launch_gather3(v.fin_pos.p, nf, v.tx.p, v.ty.p, v.tz.p, w.x.p, w.y.p, w.z.p, c->stream);
-    const BBox b = bbox_of(c, w.x.p, w.y.p, w.z.p, nf);
-    for (int k = 0; k < 3; ++k)
-      tmax = std::fmax(tmax, std::fmax(std::fabs(b.lo[k]), std::fabs(b.hi[k])));
-    L = build_hierarchy(c, nf, b, 1);
-    HIPCHK(hipGetLastError());
-    if (c->profiling) {
-      sync(c);
-      build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
-    }
+    // 1. the target: its finite points and their hierarchy (every level)
+    T = build_target(c, tgt,
+                     [&](const float* X, const float* Y, const float* Z, int rows, uint8_t* flags) {
+                       launch_finite_flags(X, Y, Z, rows, flags, c->stream);
+                     },
+                     1, "the target has no finite point");
     // 2. W
-    const size_t sbytes = (size_t)src->n * (size_t)src->stride_bytes;
-    w.raw.ensure(sbytes + (indices ? 4 * (size_t)m : 0) + 16);
-    if (sbytes) HIPCHK(hipMemcpyAsync(w.raw.p, src->xyz, sbytes, hipMemcpyHostToDevice, c->stream));
-    const int32_t* didx = nullptr;
-    if (indices && m > 0) {
-      HIPCHK(hipMemcpyAsync(w.raw.p + sbytes, indices, 4 * (size_t)m, hipMemcpyHostToDevice,
-                            c->stream));
-      didx = reinterpret_cast<const int32_t*>(w.raw.p + sbytes);
-    }
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    const float* raw = upload_raw(c, src);
+    const int32_t* didx = stage_list(c, indices, m);
+    mark(c, 0);
     const size_t mm = (size_t)std::max(m, 1);
     v.wx.ensure(mm); v.wy.ensure(mm); v.wz.ensure(mm);
     v.qa.ensure(mm); v.qb.ensure(mm); v.nn.ensure(mm); v.d2.ensure(mm);
     v.state.ensure(sizeof(IcpState));
-    if (!v.pub) HIPCHK(hipHostMalloc(&v.pub, sizeof(IcpState), hipHostMallocCoherent));
+    v.pub.ensure(sizeof(IcpState));
     st = reinterpret_cast<IcpState*>(v.state.p);
-    pub = reinterpret_cast<IcpState*>(v.pub);
+    pub = reinterpret_cast<IcpState*>(v.pub.p);
     HIPCHK(hipMemsetAsync(st, 0, sizeof(IcpState), c->stream));
-    launch_icp_gather(reinterpret_cast<const float*>(w.raw.p), sf, didx, m, xf, apply, v.wx.p,
-                      v.wy.p, v.wz.p, c->opt.icp_max_blocks, c->stream);
+    launch_icp_gather(raw, sf, didx, m, xf, apply, v.wx.p, v.wy.p, v.wz.p, c->opt.icp_max_blocks,
+                      c->stream);
     HIPCHK(hipGetLastError());
   }
 
   // one correspondence pass of W (first moved by xf when apply != 0) and its published sums: one
   // stream synchronisation
   const IcpState& pass(const IcpXf& xf, int apply, double md2) {
+    NormalsWork& w = c->nw;  // (the target as build_target left it: ax/ay/az, fin_pos)
     IcpWork& v = c->iw;
-    for (int l = 0; l < L.levels; ++l)
-      launch_icp_level(L, l, xf, apply, c->opt.icp_reversed, v.wx.p, v.wy.p, v.wz.p, m,
-                       (l & 1) ? v.qa.p : v.qb.p, (l & 1) ? v.qb.p : v.qa.p, st, v.fin_pos.p, md2,
+    for (int l = 0; l < T.L.levels; ++l)
+      launch_icp_level(T.L, l, xf, apply, c->opt.icp_reversed, v.wx.p, v.wy.p, v.wz.p, m,
+                       (l & 1) ? v.qa.p : v.qb.p, (l & 1) ? v.qb.p : v.qa.p, st, w.fin_pos.p, md2,
                        v.nn.p, v.d2.p, c->num_cus, c->opt.icp_max_blocks, c->stream);
-    launch_icp_finish(v.wx.p, v.wy.p, v.wz.p, m, v.nn.p, v.d2.p, v.tx.p, v.ty.p, v.tz.p, tmax, st,
+    launch_icp_finish(v.wx.p, v.wy.p, v.wz.p, m, v.nn.p, v.d2.p, w.ax.p, w.ay.p, w.az.p, T.tmax, st,
                       c->num_cus, c->opt.icp_max_blocks, c->stream);
     launch_icp_publish(st, pub, c->stream);
     HIPCHK(hipGetLastError());
     sync(c);
     ++syncs;
     levels_used = std::max(levels_used, 1);
-    for (int l = 1; l < L.levels; ++l)
+    for (int l = 1; l < T.L.levels; ++l)
       if (pub->qn[l] > 0) levels_used = std::max(levels_used, l + 1);
     return *pub;
   }
@@ -212,14 +156,13 @@ dlg_status dlg_icp_align(dlg_ctx* c, const dlg_points* src, const int32_t* indic
   return guarded(c, [&] {
     if (prm->max_iterations < 1) throw DlgError(DLG_ERR_INVALID, "max_iterations must be >= 1");
     const double md2 = squared_limit(prm->max_correspondence_distance);
-    if (aligned_out && out_stride_bytes != 12 && out_stride_bytes != 16)
-      throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be 12 or 16");
+    if (aligned_out) check_out_stride(out_stride_bytes);
     if (history_out && history_cap < 0) throw DlgError(DLG_ERR_INVALID, "negative history_cap");
     IcpCall ic(c);
     ic.setup(src, indices, n_indices, tgt, guess);
     IcpWork& v = c->iw;
     float fin[16];
-    for (int k = 0; k < 16; ++k) fin[k] = guess ? guess[k] : ((k % 5 == 0) ? 1.0f : 0.0f);
+    std::memcpy(fin, ic.guess, 64);
     IcpCriteria crit;
     crit.max_iterations = prm->max_iterations;
     crit.rot_thr = 1.0 - prm->transformation_epsilon;
@@ -239,7 +182,7 @@ dlg_status dlg_icp_align(dlg_ctx* c, const dlg_points* src, const int32_t* indic
         state = kIcpNoCorrespondences;
         break;
       }
-      const int e = icp_qexp(std::fmax(ic.tmax, bits_float(s.wmax)));
+      const int e = icp_qexp(std::fmax(ic.T.tmax, bits_float(s.wmax)));
       const int e2 = icp_qexp(bits_float(s.d2max));
       const IcpMoments mo = icp_moments(dig);
       icp_solve(mo, e, e2, xf.m, &mse);
@@ -274,10 +217,10 @@ dlg_status dlg_icp_align(dlg_ctx* c, const dlg_points* src, const int32_t* indic
       launch_icp_pack(v.wx.p, v.wy.p, v.wz.p, ic.m, reinterpret_cast<float*>(c->nw.out.p),
                       (int)(out_stride_bytes / 4), c->opt.icp_max_blocks, c->stream);
       HIPCHK(hipGetLastError());
-      if (c->profiling) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+      mark(c, 1);
       HIPCHK(hipMemcpyAsync(aligned_out, c->nw.out.p, obytes, hipMemcpyDeviceToHost, c->stream));
-    } else if (c->profiling) {
-      HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    } else {
+      mark(c, 1);
     }
     HIPCHK(hipGetLastError());
     sync(c);
@@ -289,11 +232,11 @@ dlg_status dlg_icp_align(dlg_ctx* c, const dlg_points* src, const int32_t* indic
       stats->levels = ic.levels_used;
       stats->n_corr = n_corr;
       stats->n_src_finite = ic.n_src_finite;
-      stats->n_tgt_finite = ic.nf;
+      stats->n_tgt_finite = ic.T.nf;
       stats->host_syncs = loop_syncs;
       stats->mse = state == kIcpNoCorrespondences && iterations == 0 ? 0.0 : mse;
       stats->fitness = fitness;
-      stats->build_ms = ic.build_ms;
+      stats->build_ms = ic.T.build_ms;
       if (c->profiling) stats->device_ms = event_ms(c, 0, 1);
     }
   });

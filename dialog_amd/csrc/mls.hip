@@ -419,13 +419,13 @@ __global__ __launch_bounds__(kBS) __attribute__((amdgpu_waves_per_eu(ORDER >= 2 
 __global__ __launch_bounds__(kBS) void k_mls_count_finite(const float* __restrict__ X,
                                                           const float* __restrict__ Y,
                                                           const float* __restrict__ Z, int n,
-                                                          unsigned long long* __restrict__ acc) {
+                                                          unsigned long long* __restrict__ dst) {
   unsigned c = 0;
   for (int64_t i = (int64_t)blockIdx.x * kBS + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBS)
     c += finite3(X[i], Y[i], Z[i]) ? 1u : 0u;
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) c += __shfl_xor(c, s, 64);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(acc + kMlsFinite, (unsigned long long)c);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(dst, (unsigned long long)c);
 }
 
 __global__ __launch_bounds__(kBS) void k_mls_need(const int32_t* __restrict__ idx, int n_list,
@@ -495,11 +495,11 @@ __global__ __launch_bounds__(kBS) void k_mls_emit(
 
 }  // namespace
 
-void launch_mls_count_finite(const float* X, const float* Y, const float* Z, int n,
-                             unsigned long long* acc, hipStream_t s) {
+void launch_count_finite(const float* X, const float* Y, const float* Z, int n,
+                         unsigned long long* dst, hipStream_t s) {
   if (n <= 0) return;
   const unsigned b = std::min(cdiv(n, kBS * 8), 2048u);
-  hipLaunchKernelGGL(k_mls_count_finite, dim3(b), dim3(kBS), 0, s, X, Y, Z, n, acc);
+  hipLaunchKernelGGL(k_mls_count_finite, dim3(b), dim3(kBS), 0, s, X, Y, Z, n, dst);
 }
 
 void launch_mls_need(const int32_t* idx, int n_list, uint8_t* need, hipStream_t s) {

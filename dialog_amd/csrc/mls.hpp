@@ -27,9 +27,6 @@ enum {
   kMlsAccWords = 8
 };
 
-// acc[kMlsFinite] += finite points of (X, Y, Z)[0..n)
-void launch_mls_count_finite(const float* X, const float* Y, const float* Z, int n,
-                             unsigned long long* acc, hipStream_t s);
 // need[idx[e]] = 1 for every list entry (need preset to 0)
 void launch_mls_need(const int32_t* idx, int n_list, uint8_t* need, hipStream_t s);
 

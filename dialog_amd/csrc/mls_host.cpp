@@ -11,14 +11,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <memory>
 #include <string>
 
-#include "driver.hpp"
+#include "cloud_call.hpp"
 #include "grid_host.hpp"
 #include "mls.hpp"
 #include "normals.hpp"
@@ -39,29 +37,16 @@ struct MlsCall {
 
   void check(const dlg_points* pts, const int32_t* indices, int64_t n_indices,
              const dlg_mls_params* prm) {
-    if (c->comm->world() > 1)
-      throw DlgError(DLG_ERR_INVALID, "moving least squares: the points are one rank's shard "
-                                      "(world > 1); the neighbours across the cut need the whole "
-                                      "cloud");
-    if (!pts || pts->n < 0 || (pts->n > 0 && !pts->xyz))
-      throw DlgError(DLG_ERR_INVALID, "points: null or negative size");
-    if (pts->stride_bytes < 12 || pts->stride_bytes % 4)
-      throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
-    if (indices && n_indices < 0) throw DlgError(DLG_ERR_INVALID, "negative n_indices");
-    if (pts->n > INT32_MAX || (indices && n_indices > INT32_MAX))
-      throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 points");
+    check_whole_cloud(c->comm->world(), "moving least squares");
+    check_points(pts);
+    n = (int)pts->n;
+    m = check_list(indices, n_indices, n);
     if (prm->polynomial_order < 1 || prm->polynomial_order > kMlsMaxOrder)
       throw DlgError(DLG_ERR_INVALID, "polynomial_order must be in 1..3");
     if (!std::isfinite(prm->search_radius) || !(prm->search_radius > 0.0f))
       throw DlgError(DLG_ERR_INVALID, "search_radius must be finite and > 0");
     if (std::isnan(prm->sqr_gauss_param))
       throw DlgError(DLG_ERR_INVALID, "sqr_gauss_param is NaN");
-    n = (int)pts->n;
-    m = (int)(indices ? n_indices : pts->n);
-    if (indices)
-      for (int i = 0; i < m; ++i)
-        if (indices[i] < 0 || indices[i] >= pts->n)
-          throw DlgError(DLG_ERR_INVALID, "index out of range");
   }
 
   // everything up to the compacted list positions of the rows in mw.sel (count: nw.counters[4]);
@@ -76,20 +61,16 @@ struct MlsCall {
     NormalsWork& w = c->nw;
     MlsWork& v = c->mw;
     const BBox b = upload_points(c, pts);  // (nw.raw, nw.x/y/z; synchronises)
-    if (indices) {
-      v.lst.ensure(m);
-      HIPCHK(hipMemcpyAsync(v.lst.p, indices, 4 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-      didx = v.lst.p;
-    }
+    didx = stage_list(c, indices, m);
     v.acc.ensure(kMlsAccWords);
     v.cnt.ensure(n); v.res_p.ensure(n); v.res_n.ensure(n);
     v.valid.ensure(m); v.sel.ensure(m); v.o_nb.ensure(m);
     GridBufs B;
     const GridDesc G = make_grid(b, (double)prm->search_radius);
     build_grid(c, n, G, 0, &B);  // (synchronises)
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    mark(c, 0);
     HIPCHK(hipMemsetAsync(v.acc.p, 0, 8 * (size_t)kMlsAccWords, c->stream));
-    launch_mls_count_finite(w.x.p, w.y.p, w.z.p, n, v.acc.p, c->stream);
+    launch_count_finite(w.x.p, w.y.p, w.z.p, n, v.acc.p + kMlsFinite, c->stream);
     const uint8_t* need = nullptr;
     if (indices) {  // (a list: only the points it names are queries; the grid holds them all)
       v.need.ensure(n);
@@ -124,7 +105,7 @@ struct MlsCall {
     (void)upload_points(c, pts);
     v.acc.ensure(kMlsAccWords);
     HIPCHK(hipMemsetAsync(v.acc.p, 0, 8 * (size_t)kMlsAccWords, c->stream));
-    launch_mls_count_finite(w.x.p, w.y.p, w.z.p, n, v.acc.p, c->stream);
+    launch_count_finite(w.x.p, w.y.p, w.z.p, n, v.acc.p + kMlsFinite, c->stream);
     HIPCHK(hipMemcpyAsync(acc, v.acc.p, sizeof(acc), hipMemcpyDeviceToHost, c->stream));
     sync(c);
   }
@@ -160,8 +141,7 @@ dlg_status dlg_moving_least_squares(dlg_ctx* c, const dlg_points* pts, const int
   *n_out = 0;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   return guarded(c, [&] {
-    if (out_stride_bytes != 12 && out_stride_bytes != 16)
-      throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be 12 or 16");
+    check_out_stride(out_stride_bytes);
     if (cap < 0) throw DlgError(DLG_ERR_INVALID, "negative cap");
     MlsCall mc(c);
     mc.run(pts, indices, n_indices, prm);
@@ -183,7 +163,7 @@ dlg_status dlg_moving_least_squares(dlg_ctx* c, const dlg_points* pts, const int
                       v.o_nrm.p, v.o_src.p, c->stream);
       HIPCHK(hipGetLastError());
     }
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    mark(c, 1);
     if (k > cap) {
       sync(c);
       mc.stats(stats);
@@ -213,49 +193,37 @@ dlg_status dlg_moving_least_squares_cloud(dlg_ctx* c, const dlg_points* pts,
                                           dlg_cloud** out, int64_t* n_out, int32_t* src_index,
                                           dlg_mls_stats* stats) {
   if (!c || !prm || !out || !n_out) return DLG_ERR_INVALID;
-  *out = nullptr;
   *n_out = 0;
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  auto cl = std::make_unique<dlg_cloud>();
-  const dlg_status s = guarded(c, [&] {
-    MlsCall mc(c);
-    mc.run(pts, indices, n_indices, prm);
-    const int64_t k = mc.n_out;
-    *n_out = k;
-    cl->ctx = c;
-    cl->n_total = k;
-    cl->n_points = k;
-    cl->id_base = id_base;
-    cl->gid_ident = true;
-    cl->n_active = k;
-    cl->pristine.ensure((size_t)std::max<int64_t>(k, 1));
-    NormalsWork& w = c->nw;
-    MlsWork& v = c->mw;
-    if (k > 0) {
-      // the rows and their ids straight into the cloud's pristine list
-      v.o_nrm.ensure((size_t)k);
-      v.o_src.ensure((size_t)k);
-      launch_mls_emit_cloud(v.sel.p, w.counters.p + 4, mc.m, mc.didx, v.res_p.p, v.res_n.p,
-                            cl->pristine.x.p, cl->pristine.y.p, cl->pristine.z.p,
-                            cl->pristine.gid.p, id_base, v.o_nrm.p, v.o_src.p, c->stream);
-      HIPCHK(hipGetLastError());
-      if (src_index)
-        HIPCHK(hipMemcpyAsync(src_index, v.o_src.p, 4 * (size_t)k, hipMemcpyDeviceToHost,
-                              c->stream));
-    }
-    if (c->profiling && mc.ran()) HIPCHK(hipEventRecord(c->ev[1], c->stream));
-    finish_upload(c, cl.get(), k);  // (synchronises)
-    if (prm->compute_normals)
-      attach_normals(c, cl.get(), k > 0 ? reinterpret_cast<const float*>(v.o_nrm.p) : nullptr, 4, 3,
-                     true);
-    mc.stats(stats);
-  });
-  if (s != DLG_OK) {
-    release_cloud_buffers(cl.get());
-    return s;
-  }
-  *out = cl.release();
-  return DLG_OK;
+  MlsCall mc(c);
+  MlsWork& v = c->mw;
+  return make_cloud(
+      c, id_base, out,
+      [&](dlg_cloud& cl) {
+        mc.run(pts, indices, n_indices, prm);
+        const int64_t k = *n_out = mc.n_out;
+        SoA& rows = cloud_rows(cl, k);
+        if (k > 0) {
+          // the rows and their ids straight into the cloud's pristine list
+          v.o_nrm.ensure((size_t)k);
+          v.o_src.ensure((size_t)k);
+          launch_mls_emit_cloud(v.sel.p, c->nw.counters.p + 4, mc.m, mc.didx, v.res_p.p, v.res_n.p,
+                                rows.x.p, rows.y.p, rows.z.p, rows.gid.p, id_base, v.o_nrm.p,
+                                v.o_src.p, c->stream);
+          HIPCHK(hipGetLastError());
+          if (src_index)
+            HIPCHK(hipMemcpyAsync(src_index, v.o_src.p, 4 * (size_t)k, hipMemcpyDeviceToHost,
+                                  c->stream));
+        }
+        if (mc.ran()) mark(c, 1);
+        return k;
+      },
+      [&](dlg_cloud& cl) {
+        if (prm->compute_normals)
+          attach_normals(c, &cl, cl.n_total > 0 ? reinterpret_cast<const float*>(v.o_nrm.p) : nullptr,
+                         4, 3, true);
+        mc.stats(stats);
+      });
 }
 
 }  // extern "C"

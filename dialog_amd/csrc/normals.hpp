@@ -115,6 +115,9 @@ void launch_flip_to_reference(float* nrm, int64_t stride_f, const float* ref, in
 // ---- preProcess (PlaneDetect.h:448-512) ----
 void launch_finite_flags(const float* X, const float* Y, const float* Z, int n, uint8_t* flags,
                          hipStream_t s);
+// *dst += the finite points of (X, Y, Z)[0..n) (mls.hip)
+void launch_count_finite(const float* X, const float* Y, const float* Z, int n,
+                         unsigned long long* dst, hipStream_t s);
 size_t select_tmp_bytes(int n);
 // out = indices i (ascending) with flags[i] != 0; *n_out (device) = their number
 hipError_t select_flagged(void* tmp, size_t tmp_bytes, const uint8_t* flags, int n, int32_t* out,

@@ -183,14 +183,6 @@ KnnLevels build_hierarchy(dlg_ctx* c, int n, const BBox& b, int k_nn) {
   return build_hierarchy_plan(c, n, b, k_nn, nullptr, -1);
 }
 
-void check_points(const dlg_points* pts) {
-  if (!pts || pts->n < 0 || (pts->n > 0 && !pts->xyz))
-    throw DlgError(DLG_ERR_INVALID, "points: null or negative size");
-  if (pts->stride_bytes < 12 || pts->stride_bytes % 4)
-    throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
-  if (pts->n > INT32_MAX / 2) throw DlgError(DLG_ERR_INVALID, "more than 2^30 points");
-}
-
 namespace {
 
 void check_normals_args(float radius, int k_nn, int mode) {
@@ -208,7 +200,7 @@ void normals_core(dlg_ctx* c, int n, const BBox& b, float radius, int k_nn, cons
 void estimate_normals(dlg_ctx* c, const dlg_points* pts, float radius, int k_nn, const float* vp_in,
                       float* out, int64_t out_stride, int mode) {
   check_normals_args(radius, k_nn, mode);
-  check_points(pts);
+  check_points(pts, "points", kMaxGridPoints);
   if (!out) throw DlgError(DLG_ERR_INVALID, "normals_out is null");
   if (out_stride != 16 && out_stride < 32) throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be 16 or >= 32");
   if (out_stride % 4) throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be a multiple of 4");
@@ -342,7 +334,7 @@ int64_t regulate_core(dlg_ctx* c, int n, const float* X, const float* Y, const f
 
 int64_t regulate_normals(dlg_ctx* c, const dlg_points* pts, float* nrm_io, int64_t stride,
                          int64_t seed, int seed_is_outward, float radius, uint8_t* processed_out) {
-  check_points(pts);
+  check_points(pts, "points", kMaxGridPoints);
   if (!nrm_io) throw DlgError(DLG_ERR_INVALID, "normals_inout is null");
   if (stride < 12 || stride % 4) throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
   if (!(radius > 0.0f && std::isfinite(radius))) throw DlgError(DLG_ERR_INVALID, "radius must be > 0");
@@ -470,8 +462,8 @@ int64_t cloud_regulate_normals(dlg_ctx* c, dlg_cloud* cl, int64_t seed, int seed
 // normal flips when Vector3f(n).dot(Vector3f(n_backup)) < 0
 void orient_normals_nn(dlg_ctx* c, const dlg_points* pts, float* nrm_io, int64_t stride,
                        const dlg_points* ref, const float* ref_nrm, int64_t ref_stride) {
-  check_points(pts);
-  check_points(ref);
+  check_points(pts, "points", kMaxGridPoints);
+  check_points(ref, "points", kMaxGridPoints);
   if (!nrm_io || (ref->n > 0 && !ref_nrm)) throw DlgError(DLG_ERR_INVALID, "normals are null");
   if (stride < 12 || stride % 4 || ref_stride < 12 || ref_stride % 4)
     throw DlgError(DLG_ERR_INVALID, "normal strides must be >= 12 and a multiple of 4");
@@ -526,7 +518,7 @@ void orient_normals_nn(dlg_ctx* c, const dlg_points* pts, float* nrm_io, int64_t
 int64_t preprocess(dlg_ctx* c, const dlg_points* pts, int translate, float min_dist, float* out,
                    int64_t out_stride, int32_t* out_idx, int64_t cap, float* translation,
                    int64_t* n_needed) {
-  check_points(pts);
+  check_points(pts, "points", kMaxGridPoints);
   if (out_stride != 12 && out_stride < 16) throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be 12 or >= 16");
   if (out_stride % 4) throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be a multiple of 4");
   if (!(min_dist == min_dist)) throw DlgError(DLG_ERR_INVALID, "min_dist is NaN");

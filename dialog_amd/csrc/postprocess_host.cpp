@@ -160,7 +160,7 @@ void check_radius(float radius) {
 
 void cluster_filter(dlg_ctx* c, const dlg_points* pts, float radius, int32_t t_cluster_num,
                     int32_t* kept_ids, int64_t cap, int64_t* n_kept) {
-  check_points(pts);
+  check_points(pts, "points", kMaxGridPoints);
   check_radius(radius);
   const int n = (int)pts->n;
   if (n == 0) return;
@@ -272,7 +272,7 @@ void post_process(dlg_ctx* c, const dlg_points* cloud, const dlg_planes* P,
                   const dlg_postprocess_params* prm, float* coeffs_out, int64_t* abs_off,
                   int32_t* abs_ids, int64_t abs_cap, int32_t* rem_ids, int64_t rem_cap,
                   int64_t* n_rem) {
-  check_points(cloud);
+  check_points(cloud, "points", kMaxGridPoints);
   check_planes(P);
   if (!prm) throw DlgError(DLG_ERR_INVALID, "params are null");
   check_radius(prm->radius_local);

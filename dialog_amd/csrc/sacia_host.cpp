@@ -12,7 +12,6 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -20,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "driver.hpp"
+#include "cloud_call.hpp"
 #include "grid_host.hpp"
 #include "normals.hpp"
 #include "sacia.hpp"
@@ -36,14 +35,6 @@ constexpr int64_t kQueueCap = 1 << 24;  // deferred pairs a queue holds: bounds 
 constexpr int kMaxBatch = 256;
 constexpr int64_t kPartCap = 1 << 26;   // entries of the search's per-slab lists (query chunks)
 constexpr int64_t kFeatBytes = 4 * kSaciaDim;
-
-void check_cloud(const dlg_points* p, const char* what) {
-  if (!p || p->n < 0 || (p->n > 0 && !p->xyz))
-    throw DlgError(DLG_ERR_INVALID, std::string(what) + ": null or negative size");
-  if (p->stride_bytes < 12 || p->stride_bytes % 4)
-    throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
-  if (p->n > INT32_MAX) throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 points");
-}
 
 void check_feat_stride(int64_t stride) {
   if (stride < kFeatBytes || stride % 4)
@@ -85,53 +76,19 @@ void upload_rows(dlg_ctx* c, const float* rows, int64_t stride, int n, DevBuf<fl
                             (size_t)n, hipMemcpyHostToDevice, c->stream));
 }
 
-// The target: its points in aw.tx/ty/tz, its packed descriptor table in aw.rows (feats null: none),
-// aw.flags = the valid rows, and the hierarchy of the valid points (nw.x/y/z, nw.lv[]).
-struct Target {
-  int nt = 0, nf = 0;
-  float tmax = 0.0f;  // the valid points' largest |coordinate|
-  KnnLevels L{};
-  double build_ms = 0.0;
-
-  void setup(dlg_ctx* c, const dlg_points* tgt, const float* feats, int64_t feat_stride, int k) {
-    NormalsWork& w = c->nw;
-    SaciaWork& a = c->aw;
-    nt = (int)tgt->n;
-    if (nt < k) throw DlgError(DLG_ERR_INVALID, "the target has fewer valid rows than k");
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t tbytes = (size_t)nt * (size_t)tgt->stride_bytes;
-    w.raw.ensure(tbytes);
-    HIPCHK(hipMemcpyAsync(w.raw.p, tgt->xyz, tbytes, hipMemcpyHostToDevice, c->stream));
-    a.tx.ensure(nt); a.ty.ensure(nt); a.tz.ensure(nt);
-    a.flags.ensure(nt); a.fin_pos.ensure(nt);
-    launch_deinterleave(reinterpret_cast<const float*>(w.raw.p), nt, tgt->stride_bytes / 4, a.tx.p,
-                        a.ty.p, a.tz.p, c->stream);
-    if (feats) upload_rows(c, feats, feat_stride, nt, a.rows);
-    launch_sacia_row_flags(feats ? a.rows.p : nullptr, kSaciaDim, a.tx.p, a.ty.p, a.tz.p, nt,
-                           a.flags.p, nullptr, c->stream);
-    w.sort_tmp.ensure(select_tmp_bytes(nt));
-    w.counters.ensure(8);
-    w.h_cnt.ensure(8);
-    HIPCHK(select_flagged(w.sort_tmp.p, w.sort_tmp.cap, a.flags.p, nt, a.fin_pos.p, w.counters.p,
-                          c->stream));
-    HIPCHK(hipMemcpyAsync(w.h_cnt.p, w.counters.p, 4, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    nf = (int)w.h_cnt.p[0];
-    if (nf < k) throw DlgError(DLG_ERR_INVALID, "the target has fewer valid rows than k");
-    w.x.ensure(nf); w.y.ensure(nf); w.z.ensure(nf);
-    launch_gather3(a.fin_pos.p, nf, a.tx.p, a.ty.p, a.tz.p, w.x.p, w.y.p, w.z.p, c->stream);
-    const BBox b = bbox_of(c, w.x.p, w.y.p, w.z.p, nf);
-    for (int d = 0; d < 3; ++d)
-      tmax = std::fmax(tmax, std::fmax(std::fabs(b.lo[d]), std::fabs(b.hi[d])));
-    L = build_hierarchy(c, nf, b, 1);
-    HIPCHK(hipGetLastError());
-    if (c->profiling) {
-      sync(c);
-      build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
-    }
-  }
-};
+// The target (build_target, cloud_call.hpp): its packed descriptor table in aw.rows (feats null:
+// none), nw.flags = the valid rows, and the hierarchy of the valid points (nw.x/y/z, nw.lv[]).
+Target sacia_target(dlg_ctx* c, const dlg_points* tgt, const float* feats, int64_t feat_stride,
+                    int k) {
+  SaciaWork& a = c->aw;
+  return build_target(c, tgt,
+                      [&](const float* X, const float* Y, const float* Z, int rows, uint8_t* flags) {
+                        if (feats) upload_rows(c, feats, feat_stride, rows, a.rows);
+                        launch_sacia_row_flags(feats ? a.rows.p : nullptr, kSaciaDim, X, Y, Z, rows,
+                                               flags, nullptr, c->stream);
+                      },
+                      k, "the target has fewer valid rows than k");
+}
 
 // computeErrorMetric of H transformations over the source in aw.sx/sy/sz: every batch is queued
 // behind the last, the sums are read back once.
@@ -144,17 +101,13 @@ struct Scorer {
   Scorer(dlg_ctx* ctx, const Target& t) : c(ctx), T(t) {}
 
   void upload_source(const dlg_points* src) {
-    NormalsWork& w = c->nw;
     SaciaWork& a = c->aw;
     n_src = (int)src->n;
     const size_t mm = (size_t)std::max(n_src, 1);
     a.sx.ensure(mm); a.sy.ensure(mm); a.sz.ensure(mm);
     if (n_src == 0) return;
-    const size_t sbytes = (size_t)n_src * (size_t)src->stride_bytes;
-    w.raw.ensure(sbytes);
-    HIPCHK(hipMemcpyAsync(w.raw.p, src->xyz, sbytes, hipMemcpyHostToDevice, c->stream));
-    launch_deinterleave(reinterpret_cast<const float*>(w.raw.p), n_src, src->stride_bytes / 4,
-                        a.sx.p, a.sy.p, a.sz.p, c->stream);
+    launch_deinterleave(upload_raw(c, src), n_src, src->stride_bytes / 4, a.sx.p, a.sy.p, a.sz.p,
+                        c->stream);
   }
 
   // queues the batches; sums[h] is valid after the caller's next synchronisation
@@ -252,17 +205,17 @@ dlg_status dlg_fpfh_knn(dlg_ctx* c, const float* queries, int64_t q_stride_bytes
     const int nq = (int)n_queries, nr = (int)n_rows;
     upload_rows(c, rows, row_stride_bytes, nr, a.rows);
     upload_rows(c, queries, q_stride_bytes, nq, a.queries);
-    a.flags.ensure(nr);
+    w.flags.ensure(nr);
     w.counters.ensure(8);
     w.h_cnt.ensure(8);
     HIPCHK(hipMemsetAsync(w.counters.p, 0, 4, c->stream));
-    launch_sacia_row_flags(a.rows.p, kSaciaDim, nullptr, nullptr, nullptr, nr, a.flags.p,
+    launch_sacia_row_flags(a.rows.p, kSaciaDim, nullptr, nullptr, nullptr, nr, w.flags.p,
                            w.counters.p, c->stream);
     HIPCHK(hipMemcpyAsync(w.h_cnt.p, w.counters.p, 4, hipMemcpyDeviceToHost, c->stream));
     const size_t no = (size_t)std::max(nq, 1) * (size_t)k;
     a.knn_d.ensure(no);
     a.knn_i.ensure(no);
-    knn_device(c, a.queries.p, nq, a.rows.p, kSaciaDim, nr, a.flags.p, k, a.knn_d.p, a.knn_i.p);
+    knn_device(c, a.queries.p, nq, a.rows.p, kSaciaDim, nr, w.flags.p, k, a.knn_d.p, a.knn_i.p);
     if (nq > 0) {
       HIPCHK(hipMemcpyAsync(idx_out, a.knn_i.p, 4 * (size_t)nq * k, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipMemcpyAsync(d_out, a.knn_d.p, 4 * (size_t)nq * k, hipMemcpyDeviceToHost, c->stream));
@@ -278,10 +231,9 @@ dlg_status dlg_sac_ia_score(dlg_ctx* c, const dlg_points* src, const dlg_points*
                             dlg_sac_ia_hypothesis* hyp_out) {
   if (!c) return DLG_ERR_INVALID;
   return guarded(c, [&] {
-    if (c->comm->world() > 1)
-      throw DlgError(DLG_ERR_INVALID, "SAC-IA: the target is one rank's shard (world > 1)");
-    check_cloud(src, "source");
-    check_cloud(tgt, "target");
+    check_whole_cloud(c->comm->world(), "SAC-IA");
+    check_points(src, "source");
+    check_points(tgt, "target");
     if (n_transforms < 0 || n_transforms > INT32_MAX || (n_transforms > 0 && (!transforms || !hyp_out)))
       throw DlgError(DLG_ERR_INVALID, "transforms: null, negative or above 2^31-1");
     if (batch < 0 || max_blocks < 0) throw DlgError(DLG_ERR_INVALID, "negative batch or max_blocks");
@@ -289,8 +241,7 @@ dlg_status dlg_sac_ia_score(dlg_ctx* c, const dlg_points* src, const dlg_points*
     const int H = (int)n_transforms;
     for (int64_t k = 0; k < 16 * (int64_t)H; ++k)
       if (!std::isfinite(transforms[k])) throw DlgError(DLG_ERR_INVALID, "a transform is not finite");
-    Target T;
-    T.setup(c, tgt, nullptr, 0, 1);
+    const Target T = sacia_target(c, tgt, nullptr, 0, 1);
     Scorer sc(c, T);
     sc.upload_source(src);
     std::vector<SaciaAcc> sums;
@@ -316,11 +267,9 @@ dlg_status dlg_sac_ia_align(dlg_ctx* c, const dlg_points* src, const float* src_
   if (!c || !prm || !final_out) return DLG_ERR_INVALID;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   return guarded(c, [&] {
-    if (c->comm->world() > 1)
-      throw DlgError(DLG_ERR_INVALID, "SAC-IA: the target is one rank's shard (world > 1); the "
-                                      "neighbours beyond its cut need the whole cloud");
-    check_cloud(src, "source");
-    check_cloud(tgt, "target");
+    check_whole_cloud(c->comm->world(), "SAC-IA");
+    check_points(src, "source");
+    check_points(tgt, "target");
     if (!src_features || !tgt_features) throw DlgError(DLG_ERR_INVALID, "null features");
     check_feat_stride(src_feat_stride);
     check_feat_stride(tgt_feat_stride);
@@ -336,13 +285,10 @@ dlg_status dlg_sac_ia_align(dlg_ctx* c, const dlg_points* src, const float* src_
       throw DlgError(DLG_ERR_INVALID, "min_sample_distance is NaN");
     if ((int64_t)nr > src->n) throw DlgError(DLG_ERR_INVALID, "nr_samples exceeds the source's size");
     const float thr = checked_threshold(prm->max_correspondence_distance);
-    if (aligned_out && out_stride_bytes != 12 && out_stride_bytes != 16)
-      throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be 12 or 16");
+    if (aligned_out) check_out_stride(out_stride_bytes);
     if (hyp_out && hyp_cap < 0) throw DlgError(DLG_ERR_INVALID, "negative hyp_cap");
     float fin[16];
-    for (int j = 0; j < 16; ++j) fin[j] = guess ? guess[j] : ((j % 5 == 0) ? 1.0f : 0.0f);
-    for (int j = 0; j < 16; ++j)
-      if (!std::isfinite(fin[j])) throw DlgError(DLG_ERR_INVALID, "the guess is not finite");
+    check_guess(guess, fin);
     const bool score_guess = !sacia_guess_is_identity(fin);
     const int n_src = (int)src->n;
     const int64_t sf = src->stride_bytes / 4, ff = src_feat_stride / 4;
@@ -387,12 +333,11 @@ dlg_status dlg_sac_ia_align(dlg_ctx* c, const dlg_points* src, const float* src_
     const int nq = (int)uniq.size();
 
     // 2. the target's valid rows, their hierarchy; the sampled source rows searched
-    Target T;
-    T.setup(c, tgt, tgt_features, tgt_feat_stride, k);
+    const Target T = sacia_target(c, tgt, tgt_features, tgt_feat_stride, k);
     SaciaWork& a = c->aw;
     int64_t syncs = 0;
     std::vector<int32_t> knn((size_t)nq * (size_t)k);
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    mark(c, 0);
     if (nq > 0) {
       std::vector<float> q((size_t)nq * kSaciaDim);
       for (int u = 0; u < nq; ++u)
@@ -401,13 +346,14 @@ dlg_status dlg_sac_ia_align(dlg_ctx* c, const dlg_points* src, const float* src_
       HIPCHK(hipMemcpyAsync(a.queries.p, q.data(), 4 * q.size(), hipMemcpyHostToDevice, c->stream));
       a.knn_d.ensure(knn.size());
       a.knn_i.ensure(knn.size());
-      knn_device(c, a.queries.p, nq, a.rows.p, kSaciaDim, T.nt, a.flags.p, k, a.knn_d.p, a.knn_i.p);
-      if (c->profiling) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+      knn_device(c, a.queries.p, nq, a.rows.p, kSaciaDim, T.nt, c->nw.flags.p, k, a.knn_d.p,
+                 a.knn_i.p);
+      mark(c, 1);
       HIPCHK(hipMemcpyAsync(knn.data(), a.knn_i.p, 4 * knn.size(), hipMemcpyDeviceToHost, c->stream));
       sync(c);
       ++syncs;
-    } else if (c->profiling) {
-      HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    } else {
+      mark(c, 1);
     }
 
     // 3. the ranks picked, the transformations solved
@@ -438,9 +384,9 @@ dlg_status dlg_sac_ia_align(dlg_ctx* c, const dlg_points* src, const float* src_
     sc.upload_source(src);
     std::vector<SaciaAcc> sums;
     SaciaState st;
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[2], c->stream));
+    mark(c, 2);
     sc.run(xfs.data(), H, thr, prm->batch, prm->max_blocks, sums, &st);
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[3], c->stream));
+    mark(c, 3);
     sync(c);
     ++syncs;
     SaciaBest best;
@@ -465,6 +411,9 @@ dlg_status dlg_sac_ia_align(dlg_ctx* c, const dlg_points* src, const float* src_
       knn_ms = event_ms(c, 0, 1);
       score_ms = event_ms(c, 2, 3);
     }
+    // (icp_fitness builds its own target over the shared staging: the de-interleaved target, nw.flags
+    // and nw.fin_pos of this call are overwritten.  Their last readers, the descriptor search and the
+    // scoring batches, were synchronised above, and nothing below reads them.)
     double fitness = 0.0;
     if (prm->compute_fitness) fitness = icp_fitness(c, src, tgt, fin, prm->fitness_max_range);
     if (hyp_out)

@@ -79,7 +79,7 @@ void pump_pending(dlg_ctx* c, int64_t ids) {
   }
 }
 
-// spin until k_publish has released `seq` into c->pub[0] (the round's results are then in
+// spin until k_publish has released `seq` into c->pub.p[0] (the round's results are then in
 // c->pub).  A stream query backs it up (no event marker on the stream: each one costs the GPU
 // a few microseconds between kernels): once the stream has drained the word must be visible; an
 // error of the stream surfaces through the query.
@@ -88,7 +88,7 @@ void wait_published(dlg_ctx* c, int32_t seq) {
   const bool poll = g->world() > 1;
   const auto t0 = std::chrono::steady_clock::now();
   for (uint32_t k = 1;; ++k) {
-    if (__atomic_load_n(c->pub, __ATOMIC_ACQUIRE) == seq) return;
+    if (__atomic_load_n(c->pub.p, __ATOMIC_ACQUIRE) == seq) return;
     // (several ranks: a failed peer's poison, or no progress within the group's timeout, ends
     // the wait -- the round's collectives may be waiting for that peer on the device)
     if (poll && (k & 255u) == 0) {
@@ -109,7 +109,7 @@ void wait_published(dlg_ctx* c, int32_t seq) {
     if ((k & 1023u) == 0) {
       const hipError_t e = hipStreamQuery(c->stream);
       if (e == hipSuccess) {
-        if (__atomic_load_n(c->pub, __ATOMIC_ACQUIRE) == seq) return;
+        if (__atomic_load_n(c->pub.p, __ATOMIC_ACQUIRE) == seq) return;
         throw DlgError(DLG_ERR_INTERNAL, "round results not visible after the round completed");
       }
       if (e != hipErrorNotReady) HIPCHK(e);
@@ -1038,14 +1038,9 @@ struct SegmentRound {
     const bool with_counts = spec_pending;
     const int nres = with_counts ? spec_Dp + spec_D + (spec_culled ? 1 : 0) : 0;
     const size_t need = (size_t)kPubRk + (W > 1 ? 2 * (size_t)W : 0) + (size_t)nres;
-    if (need > c->pub_cap) {
-      if (c->pub) HIPCHK(hipHostFree(c->pub));
-      c->pub = nullptr;
-      c->pub_cap = 0;
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->pub), std::max<size_t>(need, 16384) * 4,
-                           hipHostMallocCoherent));
-      c->pub_cap = std::max<size_t>(need, 16384);
-      c->pub[0] = 0;
+    if (need > c->pub.cap) {
+      c->pub.ensure(std::max<size_t>(need, 16384));
+      c->pub.p[0] = 0;
     }
     if (W > 1) {
       c->rk.ensure(2 * (size_t)W + 2);
@@ -1063,7 +1058,7 @@ struct SegmentRound {
     pa.res = with_counts ? c->res.p : nullptr;
     pa.nres = nres;
     pa.err = c->sel1_err.p;
-    pa.pub = c->pub;
+    pa.pub = c->pub.p;
     pa.seq = ++c->pub_seq == 0 ? ++c->pub_seq : c->pub_seq;
     return pa;
   }
@@ -1162,14 +1157,14 @@ struct SegmentRound {
 
   void read_published(const PubArgs& pa, int sk, bool timed) {
     if (trace_on()) c->t_tot = now_ms();
-    std::memcpy(c->h_tot.p, c->pub + kPubTot, 16);
-    if (c->pub[kPubErr] != 0) sel1_failed(c);  // (this round's or the last list pass's look-back)
-    std::memcpy(c->h_small.p, c->pub + kPubSmall, (size_t)pa.nsmall * sizeof(float4));
-    if (W > 1) std::memcpy(c->h_rk.p, c->pub + kPubRk, 8 * (size_t)W);
+    std::memcpy(c->h_tot.p, c->pub.p + kPubTot, 16);
+    if (c->pub.p[kPubErr] != 0) sel1_failed(c);  // (this round's or the last list pass's look-back)
+    std::memcpy(c->h_small.p, c->pub.p + kPubSmall, (size_t)pa.nsmall * sizeof(float4));
+    if (W > 1) std::memcpy(c->h_rk.p, c->pub.p + kPubRk, 8 * (size_t)W);
     check_sp_totals(c, c->h_tot.p + 2);
     if (pa.pick) {  // (with the speculative batch's counts)
-      std::memcpy(c->h_pick.p, c->pub + kPubPick, 8);
-      std::memcpy(c->h_res.p, c->pub + kPubRk + (W > 1 ? 2 * W : 0), 4 * (size_t)pa.nres);
+      std::memcpy(c->h_pick.p, c->pub.p + kPubPick, 8);
+      std::memcpy(c->h_res.p, c->pub.p + kPubRk + (W > 1 ? 2 * W : 0), 4 * (size_t)pa.nres);
     }
     // the previous round's select events precede this publish on the stream: complete now
     add_select_ms(c, sk ^ 1);

@@ -2,8 +2,8 @@
 // and dlg_statistical_outlier_removal_cloud (include/dialog_ransac.h;
 // pcl::StatisticalOutlierRemoval<PointXYZ> as Dialog/PCLViewer.cpp:334-358 calls it).
 //
-// The caller's records go up as they are; the finite points are compacted into the normals path's
-// nw.x/y/z and searched through its grid hierarchy (a level is built only once a query is sent to
+// The caller's records go up as they are; the finite points are compacted into the shared nw.x/y/z
+// (flag_points / keep_flagged, cloud_call.hpp) and searched through its grid hierarchy (a level is built only once a query is sent to
 // it).  k_sor_knn leaves one mean distance per finite point that the list names, the entries take
 // theirs, one reduction certifies the two statistics sums (else the host runs the literal loops
 // over a copy of the distances), the host derives the threshold (sor_model.hpp) and the device
@@ -11,15 +11,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <vector>
 
-#include "driver.hpp"
+#include "cloud_call.hpp"
 #include "grid_host.hpp"
 #include "normals.hpp"
 #include "segment.hpp"  // event_ms
@@ -44,27 +42,14 @@ struct SorCall {
   // everything up to the compacted kept / removed index values in sw.out_keep / sw.out_rem
   void run(const dlg_points* pts, const int32_t* indices, int64_t n_indices,
            const dlg_sor_params* prm) {
-    if (c->comm->world() > 1)
-      throw DlgError(DLG_ERR_INVALID, "statistical outlier removal: the points are one rank's "
-                                      "shard (world > 1); the neighbours across the cut need the "
-                                      "whole cloud");
-    if (!pts || pts->n < 0 || (pts->n > 0 && !pts->xyz))
-      throw DlgError(DLG_ERR_INVALID, "points: null or negative size");
-    if (pts->stride_bytes < 12 || pts->stride_bytes % 4)
-      throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
-    if (indices && n_indices < 0) throw DlgError(DLG_ERR_INVALID, "negative n_indices");
-    if (pts->n > INT32_MAX || (indices && n_indices > INT32_MAX))
-      throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 points");
+    check_whole_cloud(c->comm->world(), "statistical outlier removal");
+    check_points(pts);
+    n = (int)pts->n;
+    m = check_list(indices, n_indices, n);
     if (prm->mean_k < 1 || prm->mean_k > kSorMaxMeanK)
       throw DlgError(DLG_ERR_INVALID, "mean_k must be in 1..255");
     if (!std::isfinite(prm->stddev_mul))
       throw DlgError(DLG_ERR_INVALID, "stddev_mul must be finite");
-    n = (int)pts->n;
-    m = (int)(indices ? n_indices : pts->n);
-    if (indices)
-      for (int i = 0; i < m; ++i)
-        if (indices[i] < 0 || indices[i] >= pts->n)
-          throw DlgError(DLG_ERR_INVALID, "index out of range");
     const int K = prm->mean_k + 1;
     const auto too_few = [&](int finite) {
       return DlgError(DLG_ERR_INVALID, "fewer than mean_k + 1 finite points (" +
@@ -75,34 +60,20 @@ struct SorCall {
     NormalsWork& w = c->nw;
     SorWork& v = c->sw;
     // 1. upload, de-interleave, the finite points and their ranks
-    const size_t bytes = (size_t)n * (size_t)pts->stride_bytes;
-    w.raw.ensure(bytes + (indices ? 4 * (size_t)m : 0));
-    HIPCHK(hipMemcpyAsync(w.raw.p, pts->xyz, bytes, hipMemcpyHostToDevice, c->stream));
-    if (indices && m > 0) {
-      HIPCHK(hipMemcpyAsync(w.raw.p + bytes, indices, 4 * (size_t)m, hipMemcpyHostToDevice,
-                            c->stream));
-      didx = reinterpret_cast<const int32_t*>(w.raw.p + bytes);
-    }
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[0], c->stream));
-    v.ax.ensure(n); v.ay.ensure(n); v.az.ensure(n);
-    v.flags.ensure(n); v.fin_pos.ensure(n); v.rank.ensure(n);
-    launch_deinterleave(reinterpret_cast<const float*>(w.raw.p), n, pts->stride_bytes / 4, v.ax.p,
-                        v.ay.p, v.az.p, c->stream);
-    launch_finite_flags(v.ax.p, v.ay.p, v.az.p, n, v.flags.p, c->stream);
+    upload_raw(c, pts);
+    didx = stage_list(c, indices, m);
+    mark(c, 0);
     w.sort_tmp.ensure(select_tmp_bytes(std::max(n, m)));
-    w.counters.ensure(8);
-    w.h_cnt.ensure(8);
-    HIPCHK(select_flagged(w.sort_tmp.p, w.sort_tmp.cap, v.flags.p, n, v.fin_pos.p, w.counters.p,
-                          c->stream));
-    HIPCHK(hipMemcpyAsync(w.h_cnt.p, w.counters.p, 4, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    nf = (int)w.h_cnt.p[0];
+    nf = flag_points(c, pts, [&](const float* X, const float* Y, const float* Z, int rows,
+                                 uint8_t* flags) {
+      launch_finite_flags(X, Y, Z, rows, flags, c->stream);
+    });
     if (nf < K) throw too_few(nf);
     if (m == 0) return;  // an empty list: nothing kept, nothing removed
+    v.rank.ensure(n);
     HIPCHK(hipMemsetAsync(v.rank.p, 0xff, 4 * (size_t)n, c->stream));
-    launch_sor_rank(v.fin_pos.p, nf, v.rank.p, c->stream);
-    w.x.ensure(nf); w.y.ensure(nf); w.z.ensure(nf);
-    launch_gather3(v.fin_pos.p, nf, v.ax.p, v.ay.p, v.az.p, w.x.p, w.y.p, w.z.p, c->stream);
+    launch_sor_rank(w.fin_pos.p, nf, v.rank.p, c->stream);
+    const BBox b = keep_flagged(c, nf);
     const uint8_t* need = nullptr;
     if (indices) {  // (a list: only the finite points it names are queries; the structure holds them all)
       v.need.ensure(nf);
@@ -110,7 +81,6 @@ struct SorCall {
       launch_sor_need(didx, m, v.rank.p, v.need.p, c->stream);
       need = v.need.p;
     }
-    const BBox b = bbox_of(c, w.x.p, w.y.p, w.z.p, nf);
     // 2. the search, level by level; a level is built once a query is deferred to it
     KnnPlan plan;
     KnnLevels L = build_hierarchy_plan(c, nf, b, K, &plan, 1);
@@ -119,28 +89,20 @@ struct SorCall {
     w.dflags.ensure((size_t)nf * L.levels);
     if (L.levels > 1)
       HIPCHK(hipMemsetAsync(w.dflags.p + nf, 0, (size_t)nf * (L.levels - 1), c->stream));
-    w.sort_tmp.ensure(select_tmp_bytes(std::max(n, m)));
     v.dist_pt.ensure(nf);
     v.acc.ensure(kSorAccWords);
     HIPCHK(hipMemsetAsync(v.acc.p, 0, 8 * (size_t)kSorAccWords, c->stream));
-    auto count_flags = [&](const uint8_t* f) {
-      HIPCHK(select_flagged(w.sort_tmp.p, w.sort_tmp.cap, f, nf, w.queue.p, w.counters.p,
-                            c->stream));
-      HIPCHK(hipMemcpyAsync(w.h_cnt.p, w.counters.p, 4, hipMemcpyDeviceToHost, c->stream));
-      sync(c);
-      return (int)w.h_cnt.p[0];
-    };
     const int force = c->opt.sor_literal & 1;
     for (int l = 0; l < L.levels; ++l) {
       const int32_t* qpos = nullptr;  // level 0: every point
       int nq = nf;
       if (l > 0) {
         const uint8_t* f = w.dflags.p + (size_t)l * nf;
-        if (count_flags(f) == 0) break;  // (deferrals go one level up: nothing above either)
+        if (count_flagged(c, f, nf, w.queue.p) == 0) break;  // (deferrals go one level up: nothing above either)
         build_level(c, plan, L, l, nullptr);
         // the flagged queries in this level's cell order
         launch_gather_flags(f, L.idx[l], nf, w.processed.p, c->stream);
-        nq = count_flags(w.processed.p);
+        nq = count_flagged(c, w.processed.p, nf, w.queue.p);
         qpos = w.queue.p;
       }
       launch_sor_knn(L, l, qpos, nq, l == 0 ? need : nullptr, prm->mean_k, force, v.dist_pt.p,
@@ -188,7 +150,7 @@ struct SorCall {
     launch_sor_emit(v.sel_keep.p, w.counters.p + 4, m, didx, v.out_keep.p, c->stream);
     launch_sor_emit(v.sel_rem.p, w.counters.p + 5, m, didx, v.out_rem.p, c->stream);
     HIPCHK(hipGetLastError());
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    mark(c, 1);
     HIPCHK(hipMemcpyAsync(w.h_cnt.p + 4, w.counters.p + 4, 8, hipMemcpyDeviceToHost, c->stream));
     sync(c);
     n_keep = w.h_cnt.p[4];
@@ -260,43 +222,31 @@ dlg_status dlg_statistical_outlier_removal_cloud(dlg_ctx* c, const dlg_points* p
                                                  dlg_cloud** out, int64_t* n_kept,
                                                  int32_t* kept_out, dlg_sor_stats* stats) {
   if (!c || !prm || !out || !n_kept) return DLG_ERR_INVALID;
-  *out = nullptr;
   *n_kept = 0;
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  auto cl = std::make_unique<dlg_cloud>();
-  const dlg_status s = guarded(c, [&] {
-    SorCall sc(c);
-    sc.run(pts, indices, n_indices, prm);
-    const int64_t k = sc.n_keep;
-    *n_kept = k;
-    cl->ctx = c;
-    cl->n_total = k;
-    cl->n_points = k;
-    cl->id_base = id_base;
-    cl->gid_ident = true;
-    cl->n_active = k;
-    cl->pristine.ensure((size_t)std::max<int64_t>(k, 1));
-    if (k > 0) {
-      // the kept points and their ids straight into the cloud's pristine list
-      SorWork& v = c->sw;
-      launch_gather3(v.out_keep.p, (int)k, v.ax.p, v.ay.p, v.az.p, cl->pristine.x.p,
-                     cl->pristine.y.p, cl->pristine.z.p, c->stream);
-      launch_sor_ids(cl->pristine.gid.p, (int)k, id_base, c->stream);
-      HIPCHK(hipGetLastError());
-      if (c->profiling) HIPCHK(hipEventRecord(c->ev[1], c->stream));
-      if (kept_out)
-        HIPCHK(hipMemcpyAsync(kept_out, v.out_keep.p, 4 * (size_t)k, hipMemcpyDeviceToHost,
-                              c->stream));
-    }
-    finish_upload(c, cl.get(), k);  // (synchronises)
-    sc.stats(stats);
-  });
-  if (s != DLG_OK) {
-    release_cloud_buffers(cl.get());
-    return s;
-  }
-  *out = cl.release();
-  return DLG_OK;
+  SorCall sc(c);
+  return make_cloud(
+      c, id_base, out,
+      [&](dlg_cloud& cl) {
+        sc.run(pts, indices, n_indices, prm);
+        const int64_t k = *n_kept = sc.n_keep;
+        SoA& rows = cloud_rows(cl, k);
+        if (k > 0) {
+          // the kept points and their ids straight into the cloud's pristine list
+          NormalsWork& w = c->nw;
+          SorWork& v = c->sw;
+          launch_gather3(v.out_keep.p, (int)k, w.ax.p, w.ay.p, w.az.p, rows.x.p, rows.y.p, rows.z.p,
+                         c->stream);
+          launch_sor_ids(rows.gid.p, (int)k, id_base, c->stream);
+          HIPCHK(hipGetLastError());
+          mark(c, 1);
+          if (kept_out)
+            HIPCHK(hipMemcpyAsync(kept_out, v.out_keep.p, 4 * (size_t)k, hipMemcpyDeviceToHost,
+                                  c->stream));
+        }
+        return k;
+      },
+      [&](dlg_cloud&) { sc.stats(stats); });
 }
 
 }  // extern "C"

@@ -11,14 +11,12 @@
 // pristine list (dlg_voxel_grid_cloud).
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <memory>
 #include <vector>
 
-#include "driver.hpp"
+#include "cloud_call.hpp"
 #include "normals.hpp"
 #include "segment.hpp"  // event_ms
 #include "voxel.hpp"
@@ -40,44 +38,25 @@ struct VoxelCall {
   // validation, upload, bounds, keys, sort, runs and counts (two host synchronisations)
   void prepare(const dlg_points* pts, const int32_t* indices, int64_t n_indices,
                const dlg_voxel_params* prm) {
-    if (c->comm->world() > 1)
-      throw DlgError(DLG_ERR_INVALID, "voxel grid: the points are one rank's shard (world > 1); "
-                                      "the voxels at the cut need the whole cloud");
-    if (!pts || pts->n < 0 || (pts->n > 0 && !pts->xyz))
-      throw DlgError(DLG_ERR_INVALID, "points: null or negative size");
-    if (pts->stride_bytes < 12 || pts->stride_bytes % 4)
-      throw DlgError(DLG_ERR_INVALID, "stride_bytes must be >= 12 and a multiple of 4");
-    if (indices && n_indices < 0) throw DlgError(DLG_ERR_INVALID, "negative n_indices");
-    if (pts->n > INT32_MAX || (indices && n_indices > INT32_MAX))
-      throw DlgError(DLG_ERR_INVALID, "more than 2^31-1 points");
+    check_whole_cloud(c->comm->world(), "voxel grid");
+    check_points(pts);
+    n = check_list(indices, n_indices, pts->n);
     for (int a = 0; a < 3; ++a)
       if (!(std::isfinite(prm->leaf[a]) && prm->leaf[a] > 0.0f))
         throw DlgError(DLG_ERR_INVALID, "leaf sizes must be finite and > 0");
     if (prm->min_points_per_voxel < 0)
       throw DlgError(DLG_ERR_INVALID, "min_points_per_voxel must be >= 0");
-    n = (int)(indices ? n_indices : pts->n);
-    if (indices)
-      for (int i = 0; i < n; ++i)
-        if (indices[i] < 0 || indices[i] >= pts->n)
-          throw DlgError(DLG_ERR_INVALID, "index out of range");
     if (n == 0) return;
     NormalsWork& w = c->nw;
     VoxelWork& v = c->vw;
     // 1. upload, de-interleave + gather, finite flags
-    const size_t bytes = (size_t)pts->n * (size_t)pts->stride_bytes;
-    w.raw.ensure(bytes + (indices ? 4 * (size_t)n : 0));
-    HIPCHK(hipMemcpyAsync(w.raw.p, pts->xyz, bytes, hipMemcpyHostToDevice, c->stream));
-    const int32_t* didx = nullptr;
-    if (indices) {
-      HIPCHK(hipMemcpyAsync(w.raw.p + bytes, indices, 4 * (size_t)n, hipMemcpyHostToDevice,
-                            c->stream));
-      didx = reinterpret_cast<const int32_t*>(w.raw.p + bytes);
-    }
-    if (c->profiling) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    const float* raw = upload_raw(c, pts);
+    const int32_t* didx = stage_list(c, indices, n);
+    mark(c, 0);
     w.x.ensure(n); w.y.ensure(n); w.z.ensure(n);
     v.flags.ensure(n);
     w.rec.ensure(n);
-    launch_voxel_gather(reinterpret_cast<const float*>(w.raw.p), pts->stride_bytes / 4, didx, n,
+    launch_voxel_gather(raw, pts->stride_bytes / 4, didx, n,
                         w.x.p, w.y.p, w.z.p, w.rec.p, v.flags.p, c->stream);
     // 2. the finite list positions (ascending) and the bounds of the finite entries
     v.fin_pos.ensure(n);
@@ -152,7 +131,7 @@ struct VoxelCall {
       launch_voxel_scatter(R, v.pos_out.p, nf, v.voe.p, c->stream);
       HIPCHK(hipGetLastError());
     }
-    if (c->profiling && n > 0) HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    if (n > 0) mark(c, 1);
   }
 
   // voxel_of_entry -> the caller (enqueued; the caller synchronises)
@@ -192,8 +171,7 @@ dlg_status dlg_voxel_grid(dlg_ctx* c, const dlg_points* pts, const int32_t* indi
   *n_out = 0;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   return guarded(c, [&] {
-    if (out_stride_bytes != 12 && out_stride_bytes != 16)
-      throw DlgError(DLG_ERR_INVALID, "out_stride_bytes must be 12 or 16");
+    check_out_stride(out_stride_bytes);
     VoxelCall vc(c);
     vc.prepare(pts, indices, n_indices, prm);
     *n_out = vc.n_out;
@@ -228,36 +206,22 @@ dlg_status dlg_voxel_grid_cloud(dlg_ctx* c, const dlg_points* pts, const int32_t
                                 dlg_cloud** out, int64_t* n_out, int32_t* voxel_of_entry,
                                 dlg_voxel_stats* stats) {
   if (!c || !prm || !out || !n_out) return DLG_ERR_INVALID;
-  *out = nullptr;
   *n_out = 0;
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  auto cl = std::make_unique<dlg_cloud>();
-  const dlg_status s = guarded(c, [&] {
-    VoxelCall vc(c);
-    vc.prepare(pts, indices, n_indices, prm);
-    const int64_t k = vc.n_out;
-    *n_out = k;
-    cl->ctx = c;
-    cl->n_total = k;
-    cl->n_points = k;
-    cl->id_base = id_base;
-    cl->gid_ident = true;
-    cl->n_active = k;
-    cl->pristine.ensure((size_t)std::max<int64_t>(k, 1));
-    // the centroids and the ids straight into the cloud's pristine list (no host copy of them)
-    vc.centroids(VoxelOut{cl->pristine.x.p, cl->pristine.y.p, cl->pristine.z.p, nullptr,
-                          cl->pristine.gid.p, id_base});
-    vc.entries(voxel_of_entry != nullptr);
-    vc.copy_entries(voxel_of_entry);
-    finish_upload(c, cl.get(), k);  // (synchronises)
-    vc.stats(stats);
-  });
-  if (s != DLG_OK) {
-    release_cloud_buffers(cl.get());
-    return s;
-  }
-  *out = cl.release();
-  return DLG_OK;
+  VoxelCall vc(c);
+  return make_cloud(
+      c, id_base, out,
+      [&](dlg_cloud& cl) {
+        vc.prepare(pts, indices, n_indices, prm);
+        *n_out = vc.n_out;
+        // the centroids and the ids straight into the cloud's pristine list (no host copy of them)
+        SoA& rows = cloud_rows(cl, vc.n_out);
+        vc.centroids(VoxelOut{rows.x.p, rows.y.p, rows.z.p, nullptr, rows.gid.p, id_base});
+        vc.entries(voxel_of_entry != nullptr);
+        vc.copy_entries(voxel_of_entry);
+        return vc.n_out;
+      },
+      [&](dlg_cloud&) { vc.stats(stats); });
 }
 
 }  // extern "C"

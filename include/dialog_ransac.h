@@ -979,6 +979,10 @@ dlg_status dlg_score_benchmark(dlg_ctx* ctx, dlg_cloud* cloud, int D, int kernel
 dlg_status dlg_float_sums(dlg_ctx* ctx, const float* xyz, int64_t n, const float cin[4], int reps,
                           float sums_out[9], float coeff_out[4], int* uncertain,
                           double* ms_per_call, int64_t* walk_stats /* nullable: [9][8] */);
+/* Debugging: the bytes this process holds right now in the library's device buffers (pinned == 0)
+ * or pinned host buffers (pinned == 1), over all contexts and clouds.  The library's own count, so a
+ * test can see a leak on a device it shares with other processes.  No context. */
+int64_t dlg_debug_live_bytes(int pinned);
 /* Execution-path options of a context.  Every setting gives identical results (planes, inliers,
  * counts): they only choose among equivalent device paths, for tests and measurement.  There are
  * no environment switches in the library. */
