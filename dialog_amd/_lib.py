@@ -76,6 +76,7 @@ DLG_OPT_SOR_LITERAL = 25
 DLG_OPT_ICP_REVERSED = 26
 DLG_OPT_ICP_MAX_BLOCKS = 27
 DLG_OPT_CULL = 28
+DLG_OPT_CULL_FUSE = 29
 DLG_ICP_NOT_CONVERGED = 0
 DLG_ICP_ITERATIONS = 1
 DLG_ICP_TRANSFORM = 2

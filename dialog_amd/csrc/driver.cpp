@@ -734,7 +734,8 @@ dlg_status dlg_score_benchmark(dlg_ctx* c, dlg_cloud* cl, int D, int kernel, int
         launch_score_culled(spatial_view(cl), c->hyps.p, D, Dp, K, cthr, prune_margin(cthr, cl->amax),
                             c->res.p, c->lp.p, c->lp_n.p + kPwHeader, c->num_cus, c->stream,
                             prune_stats_ptr(c), ensure_cull(c), nullptr, nullptr, nullptr,
-                            kernel == DLG_SCORE_BOUND ? kCullBenchBound : kCullBenchCounts);
+                            kernel == DLG_SCORE_BOUND ? kCullBenchBound : kCullBenchCounts,
+                            c->opt.cull_fuse != 0);
       } else if (variant == kScorePruned) {
         if (!cl->sp_valid) throw DlgError(DLG_ERR_INVALID, "cloud has no spatial copy");
         c->lp.ensure((size_t)sp_supers(cl->sp_n) * prune_list_stride(D) + 1);
@@ -803,6 +804,7 @@ const OptRow kOptions[] = {
     OPT_BOOL(DLG_OPT_ICP_REVERSED, icp_reversed),
     OPT(DLG_OPT_ICP_MAX_BLOCKS, icp_max_blocks, 0, 65536, "0..65536"),
     OPT(DLG_OPT_CULL, cull, 0, kMaxHypPerLaunch, "0..4096"),
+    OPT_BOOL(DLG_OPT_CULL_FUSE, cull_fuse),
 };
 #undef OPT_BOOL
 #undef OPT

@@ -280,6 +280,8 @@ struct PathOptions {
   int cull = 1;             // DLG_OPT_CULL: probability-1 rounds score only the hypotheses whose
                             // tile bound can still win (spatial.hpp): 0 off, 1 = the 64 largest
                             // bounds first, n >= 2 = the n largest first
+  int cull_fuse = 1;        // DLG_OPT_CULL_FUSE (A/B): a culled round's selections run in the last
+                            // workgroup of the launch before them (spatial.hpp); 0 = one launch each
 };
 
 struct dlg_ctx {

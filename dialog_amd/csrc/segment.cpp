@@ -705,9 +705,9 @@ struct SegmentRound {
       if (spec_culled) {
         const int K = cull_k(c->opt.cull);
         launch_score_culled(spatial_view(cl), hyps_s, Ds, Dp, K, P.cthr, P.pmargin, counts_s, c->lp.p,
-                            c->lp_n.p + kPwHeader, c->num_cus, c->stream, prune_stats_ptr(c), ensure_cull(c), &pk,
-                            P.ext_ev ? c->ev[0] : nullptr,
-                            P.ext_ev ? c->ev[1] : nullptr, kCullRound);
+                            c->lp_n.p + kPwHeader, c->num_cus, c->stream, prune_stats_ptr(c),
+                            ensure_cull(c), &pk, P.ext_ev ? c->ev[0] : nullptr,
+                            P.ext_ev ? c->ev[1] : nullptr, kCullRound, c->opt.cull_fuse != 0);
       } else {
         launch_score_pruned(spatial_view(cl), hyps_s, Ds, P.cthr, P.pmargin, cl->amax, counts_s,
                             c->lp.p, c->lp_n.p + kPwHeader, c->num_cus, c->stream, prune_stats_ptr(c),

@@ -1242,14 +1242,12 @@ __global__ __launch_bounds__(BS) void k_score_tiles_ex(
 // workgroup b takes super-tiles b + gridDim.x (w + 16 k): with gridDim.x a multiple of 8 they are
 // those of XCD b & 7, as in the scorer.
 constexpr int kBtBS = 1024;
-__global__ __launch_bounds__(kBtBS) void k_bound_tiles(const float4* __restrict__ tiles,
-                                                       int ntiles, const uint16_t* __restrict__ lp,
-                                                       int ls, const int32_t* __restrict__ lp_n,
-                                                       int nsup, const HypRec* __restrict__ hyps,
-                                                       int D, float margin,
-                                                       int32_t* __restrict__ nt) {
+// (s_nt: the workgroup's kMaxHypPerLaunch counters, in the kernel's LDS)
+__device__ __forceinline__ void bound_tiles_body(
+    const float4* __restrict__ tiles, int ntiles, const uint16_t* __restrict__ lp, int ls,
+    const int32_t* __restrict__ lp_n, int nsup, const HypRec* __restrict__ hyps, int D,
+    float margin, int32_t* __restrict__ nt, int32_t* s_nt) {
   __shared__ float4 s_cf[kMaxHypPerLaunch];
-  __shared__ int32_t s_nt[kMaxHypPerLaunch];
   __shared__ float4 s_tb[kBtBS / kWave][kSuperTiles];
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
   for (int j = threadIdx.x; j < D; j += kBtBS) {
@@ -1310,6 +1308,16 @@ __global__ __launch_bounds__(kBtBS) void k_bound_tiles(const float4* __restrict_
     if (s_nt[j]) atomicAdd(&nt[j], s_nt[j]);
 }
 
+__global__ __launch_bounds__(kBtBS) void k_bound_tiles(const float4* __restrict__ tiles,
+                                                       int ntiles, const uint16_t* __restrict__ lp,
+                                                       int ls, const int32_t* __restrict__ lp_n,
+                                                       int nsup, const HypRec* __restrict__ hyps,
+                                                       int D, float margin,
+                                                       int32_t* __restrict__ nt) {
+  __shared__ int32_t s_nt[kMaxHypPerLaunch];
+  bound_tiles_body(tiles, ntiles, lp, ls, lp_n, nsup, hyps, D, margin, nt, s_nt);
+}
+
 // k_score_supers: the exact counts of a culled round's candidate set (a few dozen planes, their
 // number known only on the device).  k_score_tiles_ex is built for hundreds of near planes per
 // tile: with 64 planes its passes run nearly empty and each 2-tile item waits out its own chain of
@@ -1322,16 +1330,15 @@ __global__ __launch_bounds__(kBtBS) void k_bound_tiles(const float4* __restrict_
 // the tile sphere would rule out has no inlier, so evaluating it adds nothing to the count.
 constexpr int kSsBS = 1024;
 constexpr int kSsPer = kSuperP / kWave;  // points per lane
-__global__ __launch_bounds__(kSsBS) void k_score_supers(
+// (D planes, D > 0; every thread of the workgroup)
+__device__ __forceinline__ void score_supers_body(
     const float* __restrict__ X, const float* __restrict__ Y, const float* __restrict__ Z, int n,
     const float4* __restrict__ supers, int nsup, const HypRec* __restrict__ hyps,
-    const int32_t* __restrict__ D_dev, float cthr, float margin, int32_t* __restrict__ counts,
+    int D, float cthr, float margin, int32_t* __restrict__ counts,
     unsigned long long* __restrict__ stats) {
   __shared__ float4 s_cf[kMaxHypPerLaunch];
   __shared__ int32_t s_cnt[kMaxHypPerLaunch];
   __shared__ unsigned long long s_st[3];
-  const int D = *D_dev;
-  if (D == 0) return;
   if (threadIdx.x < 3) s_st[threadIdx.x] = 0;
   // (stats, dlg_prune_stats: planes tested against super-tile spheres as [1] list entries, tiles
   // visited [2], (tile, plane) pairs evaluated [4] -- all the tiles of a near super-tile -- and
@@ -1389,6 +1396,16 @@ __global__ __launch_bounds__(kSsBS) void k_score_supers(
     atomicAdd(&stats[3], (s_st[2] + 127ull) / 128ull);
     atomicAdd(&stats[4], s_st[2]);
   }
+}
+
+__global__ __launch_bounds__(kSsBS) void k_score_supers(
+    const float* __restrict__ X, const float* __restrict__ Y, const float* __restrict__ Z, int n,
+    const float4* __restrict__ supers, int nsup, const HypRec* __restrict__ hyps,
+    const int32_t* __restrict__ D_dev, float cthr, float margin, int32_t* __restrict__ counts,
+    unsigned long long* __restrict__ stats) {
+  const int D = *D_dev;
+  if (D == 0) return;
+  score_supers_body(X, Y, Z, n, supers, nsup, hyps, D, cthr, margin, counts, stats);
 }
 
 constexpr int kCullBS = 1024;
@@ -1584,6 +1601,242 @@ __global__ __launch_bounds__(kCullBS) void k_cull_tail(int32_t* __restrict__ res
 __global__ void k_cull_bound_out(const int32_t* __restrict__ nt, int D, int32_t* __restrict__ counts) {
   const int h = blockIdx.x * blockDim.x + threadIdx.x;
   if (h < D) counts[h] = (int32_t)min(32ll * nt[h], (long long)INT_MAX);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The fused sequence (DLG_OPT_CULL_FUSE, the default): the same sets, counts and pick in four
+// launches.  Each selection runs in the last workgroup of the launch before it, found by a ticket
+// as in k_score_tiles_ex's fused pick: a workgroup's atomic flushes are acknowledged
+// (s_waitcnt 0), it takes a device-scope ticket, and the one that draws the last ticket reads the
+// sums with device-coherent loads and resets the ticket word.  No workgroup waits for another.
+//   k_prune_supers       : as in the unculled path (it also zeroes nt);
+//   k_bound_tiles_pick   : k_bound_tiles; its last workgroup picks set A (cull_pick_a_radix);
+//   k_score_supers_f<1>  : exact counts of A; its last workgroup does k_cull_pick_b's work;
+//   k_score_supers_f<2>  : exact counts of B; its last workgroup does k_cull_tail's work.
+// (One kernel for prune + bound -- the hyper list kept in LDS, no lp / lp_n -- measured slower
+// than the two launches it replaces: DESIGN.md §7.)
+constexpr int kCullTicket = 3;  // CullBufs::hdr[3], [4], [5]: the ticket words of the three launches
+
+// true in the workgroup that draws the launch's last ticket (all threads call; the flushes of
+// every thread are acknowledged first)
+__device__ __forceinline__ bool cull_last_workgroup(int32_t* ticket) {
+  __shared__ unsigned s_ticket;
+  unsigned* tk = reinterpret_cast<unsigned*>(ticket);
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+  if (threadIdx.x == 0)
+    s_ticket = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (s_ticket != gridDim.x - 1) return false;
+  if (threadIdx.x == 0) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
+}
+
+// Set A as k_cull_pick_a defines it, by a radix select on nt: 10 bits per pass from the top bit
+// nt can have (two passes at C3's 312500 tiles), one LDS histogram of 1024 bins per pass (s_hist:
+// kMaxHypPerLaunch zeroed words, visible to the workgroup), the bin that holds the K-th largest
+// found by a block scan from the top bin.  That leaves nt_K and how many hypotheses with nt ==
+// nt_K belong to the set: the first ones by index (a block prefix over the tie flags), which is
+// the order of k_cull_pick_a's key.  nt is read with device-coherent loads.
+static_assert(kCullBS == 1024 && kBtBS == kCullBS && kMaxHypPerLaunch == 4 * 1024,
+              "one bin per thread, <= 4 passes; the selection runs in a bound workgroup");
+__device__ __forceinline__ void cull_pick_a_radix(const HypRec* __restrict__ hyps,
+                                                  const int32_t* __restrict__ good, int D, int K,
+                                                  int ntiles, const CullBufs& cb, int32_t* s_hist) {
+  __shared__ int s_w[kCullBS / kWave];
+  __shared__ int s_sel[2];
+  __shared__ int s_ng;
+  const int t = threadIdx.x, h0 = t * kCullPer;
+  if (t == 0) s_ng = 0;
+  bool g[kCullPer];
+  int v[kCullPer];
+  // (flags and counts loaded together: one memory round trip, not two)
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) g[i] = h0 + i < D && good[h0 + i] != 0;
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i)
+    v[i] = h0 + i < D ? __hip_atomic_load(cb.nt + h0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+  __syncthreads();
+  {
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < kCullPer; ++i) c += (int)__popcll(ballot(g[i]));
+    if ((t & (kWave - 1)) == 0 && c) atomicAdd(&s_ng, c);
+  }
+  const int bits = 32 - __builtin_clz((uint32_t)max(ntiles, 1));  // nt <= ntiles < 2^bits
+  const int npass = (bits + 9) / 10;
+  int need = K, n_good = 0;
+  uint32_t pref = 0u;  // the digits found so far; the need-th largest among the keys under it
+  for (int p = 0; p < npass; ++p) {
+    const int shift = 10 * (npass - 1 - p);
+    int32_t* hist = s_hist + 1024 * p;
+#pragma unroll
+    for (int i = 0; i < kCullPer; ++i)
+      if (g[i] && ((uint32_t)v[i] >> shift >> 10) == pref) atomicAdd(&hist[((uint32_t)v[i] >> shift) & 1023u], 1);
+    __syncthreads();
+    if (p == 0) {
+      n_good = s_ng;
+      if (n_good <= K) break;  // (uniform: every good hypothesis)
+    }
+    const int bin = 1023 - t, c = hist[bin];
+    int tot;
+    const int excl = cull_block_excl(c, s_w, &tot);  // the keys in the bins above `bin`
+    if (excl < need && excl + c >= need) {
+      s_sel[0] = bin;
+      s_sel[1] = need - excl;
+    }
+    __syncthreads();
+    pref = pref << 10 | (uint32_t)s_sel[0];
+    need = s_sel[1];
+  }
+  bool in[kCullPer];
+  if (n_good <= K) {
+#pragma unroll
+    for (int i = 0; i < kCullPer; ++i) in[i] = g[i];
+  } else {
+    // pref = nt_K; of the hypotheses with nt == nt_K the first `need` by index
+    int ce = 0;
+#pragma unroll
+    for (int i = 0; i < kCullPer; ++i) ce += g[i] && (uint32_t)v[i] == pref ? 1 : 0;
+    int tot;
+    int rank = cull_block_excl(ce, s_w, &tot);
+#pragma unroll
+    for (int i = 0; i < kCullPer; ++i) {
+      const bool tie = g[i] && (uint32_t)v[i] == pref;
+      in[i] = g[i] && ((uint32_t)v[i] > pref || (tie && rank < need));
+      rank += tie ? 1 : 0;
+    }
+  }
+  int c = 0;
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) c += in[i] ? 1 : 0;
+  int n_a;
+  int pos = cull_block_excl(c, s_w, &n_a);
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) {
+    const int h = h0 + i;
+    if (h >= D) continue;
+    cb.mark[h] = in[i] ? 1 : 0;
+    if (in[i]) {
+      cb.hyp_a[pos] = hyps[h];
+      cb.idx_a[pos] = h;
+      cb.cnt_a[pos] = 0;
+      ++pos;
+    }
+  }
+  if (t == 0) {
+    cb.hdr[0] = n_a;
+    cb.hdr[2] = n_good;
+  }
+}
+
+// k_bound_tiles_pick: k_bound_tiles, and set A selected by its last workgroup (the counters'
+// LDS, flushed, holds the histograms)
+__global__ __launch_bounds__(kBtBS) void k_bound_tiles_pick(
+    const float4* __restrict__ tiles, int ntiles, const uint16_t* __restrict__ lp, int ls,
+    const int32_t* __restrict__ lp_n, int nsup, const HypRec* __restrict__ hyps,
+    const int32_t* __restrict__ good, int D, float margin, int K, CullBufs cb) {
+  __shared__ int32_t s_nt[kMaxHypPerLaunch];
+  bound_tiles_body(tiles, ntiles, lp, ls, lp_n, nsup, hyps, D, margin, cb.nt, s_nt);
+  if (!cull_last_workgroup(cb.hdr + kCullTicket)) return;
+  for (int j = threadIdx.x; j < kMaxHypPerLaunch; j += kBtBS) s_nt[j] = 0;
+  cull_pick_a_radix(hyps, good, D, K, ntiles, cb, s_nt);
+}
+
+// k_cull_pick_b's work in the last workgroup of pass A: A's counts (summed by this launch's
+// atomics: device-coherent loads) into res, B compacted, n_b
+__device__ __forceinline__ void cull_pick_b_body(const HypRec* __restrict__ hyps,
+                                                 const int32_t* __restrict__ good, int D,
+                                                 int32_t* __restrict__ res, const CullBufs& cb) {
+  __shared__ int s_w[kCullBS / kWave];
+  __shared__ int s_max;
+  const int n_a = cb.hdr[0];
+  const int h0 = threadIdx.x * kCullPer;
+  // (the batch's flags, marks and bounds do not depend on A's counts: loaded beside them)
+  bool cand[kCullPer];
+  long long bnd[kCullPer];
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) {
+    const int h = h0 + i;
+    int gd = 0, mk = 1, nt = 0;
+    if (h < D) { gd = good[h]; mk = cb.mark[h]; nt = cb.nt[h]; }
+    cand[i] = gd != 0 && mk == 0;
+    bnd[i] = 32ll * nt;
+  }
+  if (threadIdx.x == 0) s_max = 0;
+  __syncthreads();
+  int mx = 0;
+  for (int i = threadIdx.x; i < n_a; i += kCullBS) {
+    const int cnt = __hip_atomic_load(cb.cnt_a + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    res[cb.idx_a[i]] = cnt;
+    mx = max(mx, cnt);
+  }
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) mx = max(mx, __shfl_xor(mx, o));
+  if ((threadIdx.x & (kWave - 1)) == 0 && mx > 0) atomicMax(&s_max, mx);
+  __syncthreads();
+  const long long b_cnt = s_max;
+  bool in[kCullPer];
+  int c = 0;
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) {
+    in[i] = cand[i] && bnd[i] >= b_cnt;
+    c += in[i] ? 1 : 0;
+  }
+  int n_b;
+  int pos = cull_block_excl(c, s_w, &n_b);
+#pragma unroll
+  for (int i = 0; i < kCullPer; ++i) {
+    if (!in[i]) continue;
+    cb.hyp_b[pos] = hyps[h0 + i];
+    cb.idx_b[pos] = h0 + i;
+    cb.cnt_b[pos] = 0;
+    ++pos;
+  }
+  if (threadIdx.x == 0) cb.hdr[1] = n_b;
+}
+
+// k_cull_tail's work in the last workgroup of pass B (B's counts by device-coherent loads)
+__device__ __forceinline__ void cull_tail_body(int32_t* __restrict__ res, int D, int Dp,
+                                               const CullBufs& cb, const PickArgs& pick_args) {
+  const int n_a = cb.hdr[0], n_b = cb.hdr[1], n_good = cb.hdr[2];
+  for (int i = threadIdx.x; i < n_b; i += kCullBS)
+    __hip_atomic_store(res + cb.idx_b[i],
+                       __hip_atomic_load(cb.cnt_b + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!pick_args.out) return;  // (dlg_score_benchmark: no round, no counters, no pick)
+  if (threadIdx.x == 0) {
+    cb.stats[0] += 1ull;
+    cb.stats[1] += (unsigned long long)n_a;
+    cb.stats[2] += (unsigned long long)n_b;
+    cb.stats[3] += (unsigned long long)(n_good - n_a - n_b);
+    cb.stats[4] += n_b > 0 ? 1ull : 0ull;
+    cb.stats[5] += kCullFallbackDiv * (n_a + n_b) > D ? 1ull : 0ull;
+    res[Dp + D] = n_a + n_b;
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+  pick_body<kCullBS, true>(pick_args);
+}
+
+// k_score_supers_f<TAIL>: k_score_supers, then in the launch's last workgroup the selection that
+// follows it: TAIL 1 = set B, 2 = the tail.  With no plane (n_b == 0 in 16 of C3's 20 rounds)
+// nothing is summed and workgroup 0 goes on by itself.  hyps / good / D: the whole batch (the
+// selections); hset / n_dev: the set scored.
+static_assert(kSsBS == kCullBS, "the selections run in a scoring workgroup");
+template <int TAIL>
+__global__ __launch_bounds__(kSsBS) void k_score_supers_f(
+    const float* __restrict__ X, const float* __restrict__ Y, const float* __restrict__ Z, int n,
+    const float4* __restrict__ supers, int nsup, const HypRec* __restrict__ hset,
+    const int32_t* __restrict__ n_dev, float cthr, float margin, int32_t* __restrict__ counts,
+    unsigned long long* __restrict__ stats, const HypRec* __restrict__ hyps,
+    const int32_t* __restrict__ good, int D, int Dp, int32_t* __restrict__ res, CullBufs cb,
+    PickArgs pick_args) {
+  const int S = *n_dev;  // planes of the set (uniform over the grid)
+  if (S > 0) score_supers_body(X, Y, Z, n, supers, nsup, hset, S, cthr, margin, counts, stats);
+  if (S > 0 ? !cull_last_workgroup(cb.hdr + kCullTicket + TAIL) : blockIdx.x != 0) return;
+  if constexpr (TAIL == 1) cull_pick_b_body(hyps, good, D, res, cb);
+  else cull_tail_body(res, D, Dp, cb, pick_args);
 }
 
 __global__ void k_gather_nrm(const float4* __restrict__ src, const int32_t* __restrict__ order,
@@ -1800,20 +2053,33 @@ void launch_score_culled(const SpatialView& v, const HypRec* hyps, int D, int Dp
                          float margin, int32_t* res, uint16_t* lp, int32_t* lp_n, int num_cus,
                          hipStream_t s, unsigned long long* pstats, const CullBufs& cb,
                          const PickArgs* pick, hipEvent_t ev_start, hipEvent_t ev_stop,
-                         CullMode mode) {
+                         CullMode mode, bool fuse) {
   const PrunedShape sh = pruned_shape(v.n, num_cus);
   const int ls = prune_list_stride(D);
   int32_t* work = lp_n - kPwHeader;
   const int32_t* good = res + Dp;
   const int ntiles = (int)sp_tiles(v.n);
+  const bool bound_only = mode == kCullBenchBound;
+  // (the exact passes and k_bound_tiles: one wave per super-tile)
+  int64_t gb = std::max<int64_t>(1, std::min<int64_t>(num_cus, (sh.ns + kBtBS / kWave - 1) / (kBtBS / kWave)));
+  if (gb >= 8) gb = (gb + 7) / 8 * 8;
+  const PickArgs pk = mode == kCullRound && pick ? *pick : PickArgs{};
   // all D planes against the super-tiles (no class order: the bound pass deals super-tiles to
   // waves by index), then the bound pass
   DLG_LAUNCH_EV(k_prune_supers, dim3(sh.ga), dim3(kPrBS), 0, s, ev_start, nullptr, v.supers,
                 (int)sh.ns, hyps, D, ls, margin, sh.H, lp, lp_n, work, 0, (float4*)nullptr,
                 cb.nt, D);
-  int64_t gb = std::max<int64_t>(1, std::min<int64_t>(num_cus, (sh.ns + kBtBS / kWave - 1) / (kBtBS / kWave)));
-  if (gb >= 8) gb = (gb + 7) / 8 * 8;
-  const bool bound_only = mode == kCullBenchBound;
+  if (fuse && !bound_only) {
+    hipLaunchKernelGGL(k_bound_tiles_pick, dim3((unsigned)gb), dim3(kBtBS), 0, s, v.tiles, ntiles,
+                       lp, ls, lp_n, (int)sh.ns, hyps, good, D, margin, K, cb);
+    hipLaunchKernelGGL(k_score_supers_f<1>, dim3((unsigned)gb), dim3(kSsBS), 0, s, v.x, v.y, v.z,
+                       (int)v.n, v.supers, (int)sh.ns, cb.hyp_a, cb.hdr, cthr, margin, cb.cnt_a,
+                       pstats, hyps, good, D, Dp, res, cb, PickArgs{});
+    DLG_LAUNCH_EV(k_score_supers_f<2>, dim3((unsigned)gb), dim3(kSsBS), 0, s, nullptr, ev_stop,
+                  v.x, v.y, v.z, (int)v.n, v.supers, (int)sh.ns, cb.hyp_b, cb.hdr + 1, cthr, margin,
+                  cb.cnt_b, pstats, hyps, good, D, Dp, res, cb, pk);
+    return;
+  }
   DLG_LAUNCH_EV(k_bound_tiles, dim3((unsigned)gb), dim3(kBtBS), 0, s, nullptr, nullptr,
                 v.tiles, ntiles, lp, ls, lp_n, (int)sh.ns, hyps, D, margin, cb.nt);
   if (bound_only) {
@@ -1821,7 +2087,6 @@ void launch_score_culled(const SpatialView& v, const HypRec* hyps, int D, int Dp
                   ev_stop, cb.nt, D, res);
     return;
   }
-  // (one wave per super-tile, as the bound pass)
   auto exact_pass = [&](const HypRec* h, const int32_t* n_dev, int32_t* counts) {
     hipLaunchKernelGGL(k_score_supers, dim3((unsigned)gb), dim3(kSsBS), 0, s, v.x, v.y, v.z,
                        (int)v.n, v.supers, (int)sh.ns, h, n_dev, cthr, margin, counts, pstats);
@@ -1830,7 +2095,6 @@ void launch_score_culled(const SpatialView& v, const HypRec* hyps, int D, int Dp
   exact_pass(cb.hyp_a, cb.hdr, cb.cnt_a);
   hipLaunchKernelGGL(k_cull_pick_b, dim3(1), dim3(kCullBS), 0, s, hyps, good, D, res, cb);
   exact_pass(cb.hyp_b, cb.hdr + 1, cb.cnt_b);
-  DLG_LAUNCH_EV(k_cull_tail, dim3(1), dim3(kCullBS), 0, s, nullptr, ev_stop, res, D, Dp, cb,
-                mode == kCullRound && pick ? *pick : PickArgs{});
+  DLG_LAUNCH_EV(k_cull_tail, dim3(1), dim3(kCullBS), 0, s, nullptr, ev_stop, res, D, Dp, cb, pk);
 }
 }  // namespace dlg

@@ -136,6 +136,12 @@ void launch_score_pruned(const SpatialView& v, const HypRec* hyps, int D, float 
 // -> k_cull_pick_b -> k_score_supers (B) -> k_cull_tail (counts scattered into res, then the
 // pick).  The exact passes read their plane counts from device memory (hdr[0], hdr[1]); a pass
 // with no plane returns at once.  Every dependency is a launch boundary on the one stream.
+// That is DLG_OPT_CULL_FUSE 0.  The default (1) runs the three one-workgroup steps in the last
+// workgroup of the launch before each -- found by a ticket (hdr[3..5]) once its workgroups' sums are
+// acknowledged; no workgroup waits for another -- so the order is k_prune_supers ->
+// k_bound_tiles_pick (bound + set A) -> k_score_supers_f<1> (A + set B) -> k_score_supers_f<2>
+// (B + tail); set A is found by a radix select on nt instead of k_cull_pick_a's two-bit steps.
+// Same sets, counts, pick and counters.
 constexpr int kCullDefaultK = 64;
 // DLG_OPT_CULL's value (>= 1) as K
 inline int cull_k(int opt) { return opt <= 1 ? kCullDefaultK : opt; }
@@ -143,10 +149,12 @@ inline int cull_k(int opt) { return opt <= 1 ? kCullDefaultK : opt; }
 // rest of the call.  k_score_supers prunes by super-tile only and costs ~9x the tile scorer per
 // plane (C3: 0.51 against 0.056 us), and a culled round spends ~0.36 of the unculled round before
 // any exact test (prune, bound, selection): it pays up to (1 - 0.36) / 9.2 = D / 14 planes
-// (DESIGN.md §7).
+// (DESIGN.md §7).  With the fused selections the share before any exact test is 0.25:
+// (1 - 0.25) / 9.2 = D / 12, and 16 is still the power of two that does not overshoot it.
 constexpr int kCullFallbackDiv = 16;
 inline bool cull_falls_back(int64_t scored, int64_t D) { return kCullFallbackDiv * scored > D; }
-constexpr int kCullHdrWords = 16;  // [0] n_a, [1] n_b, [2] good hypotheses of the batch
+constexpr int kCullHdrWords = 16;  // [0] n_a, [1] n_b, [2] good hypotheses of the batch,
+                                   // [3..5] the fused launches' tickets (zero between launches)
 // dlg_cull_stats' counters: rounds culled, hypotheses scored in pass A, in pass B, good hypotheses
 // culled, rounds with a non-empty pass B, rounds that scored more than D / kCullFallbackDiv
 // (fell back).  Only rounds count: dlg_score_benchmark's ids leave the counters alone
@@ -175,7 +183,7 @@ void launch_score_culled(const SpatialView& v, const HypRec* hyps, int D, int Dp
                          float margin, int32_t* res, uint16_t* lp, int32_t* lp_n, int num_cus,
                          hipStream_t s, unsigned long long* pstats, const CullBufs& cb,
                          const PickArgs* pick, hipEvent_t ev_start, hipEvent_t ev_stop,
-                         CullMode mode);
+                         CullMode mode, bool fuse);  // fuse: DLG_OPT_CULL_FUSE
 // (np_lim_max, the NORMAL_PLANE prefilter limit of the largest w: np_limit_host.hpp)
 // gather the pristine normals into the Morton-ordered copy: dst[i] = src[order[i]]
 void launch_gather_nrm(const float4* src, const int32_t* order, int64_t n, float4* dst,

@@ -59,7 +59,8 @@ extern "C" {
  * option, entry and benchmark ids); dlg_fpfh_estimate, dlg_cloud_fpfh, dlg_fpfh_params,
  * dlg_fpfh_stats (same ABI version: added entries); dlg_sac_ia_align, dlg_sac_ia_score,
  * dlg_fpfh_knn, dlg_sac_ia_params_default, dlg_sac_ia_params, dlg_sac_ia_hypothesis,
- * dlg_sac_ia_stats (same ABI version: added entries) */
+ * dlg_sac_ia_stats (same ABI version: added entries); DLG_OPT_CULL_FUSE (same ABI version: an added
+ * option) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -1110,6 +1111,13 @@ enum {
                                computed (dlg_score_samples always computes all).  A round that
                                scores more than 1/16 of its batch exactly turns culling off for the rest of
                                the call */
+  ,
+  DLG_OPT_CULL_FUSE = DLG_OPT_CULL + 1 /* (29) A/B: 1 (default) = a culled round's scoring runs in
+                               four launches (prune; tile bound + first candidate set; first exact
+                               pass + second set; second exact pass + pick), each selection made by
+                               the last workgroup of the launch before it; 0 = the seven-launch
+                               sequence (one launch per step).  Same counts, same pick, same
+                               dlg_cull_stats for either value */
 };
 enum { DLG_TILE_EXACT = 0, DLG_TILE_BF16 = 1, DLG_TILE_MFMA = 2 };
 enum { DLG_SCORE_EXACT = 0, DLG_SCORE_BF16 = 1, DLG_SCORE_PRUNED = 2,
