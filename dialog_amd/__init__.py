@@ -20,6 +20,8 @@ from .preprocess import (preprocess, remove_redundant_points, voxel_grid,  # noq
 from .registration import (fpfh_knn, icp_align, icp_correspondences,  # noqa: F401
                            sac_ia_align, sac_ia_score)
 from .features import cloud_fpfh, fpfh_estimation  # noqa: F401
+from .gauss_sphere import (cloud_gauss_sphere_segment, gauss_sphere_params,  # noqa: F401
+                           gauss_sphere_segment, gauss_sphere_space, gauss_sphere_vote)
 from .postprocess import (PostProcessParams, cluster_filter, plane_border,  # noqa: F401
                           post_process_planes, refit_planes)
 from ._lib import DLG_REFIT_FAST, DLG_REFIT_PCL, LIB_PATH  # noqa: F401
@@ -41,4 +43,5 @@ __all__ = ["Context", "Cloud", "SACSegmentation", "extract_planes", "segment_clo
            "statistical_outlier_removal", "statistical_outlier_removal_cloud",
            "moving_least_squares", "moving_least_squares_cloud", "icp_align",
            "icp_correspondences", "fpfh_estimation", "cloud_fpfh", "sac_ia_align", "sac_ia_score",
-           "fpfh_knn"]
+           "fpfh_knn", "gauss_sphere_vote", "gauss_sphere_segment", "cloud_gauss_sphere_segment",
+           "gauss_sphere_space", "gauss_sphere_params"]

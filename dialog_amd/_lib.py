@@ -45,6 +45,8 @@ SYMBOLS = [
     "dlg_fpfh_estimate", "dlg_cloud_fpfh",
     "dlg_sac_ia_params_default", "dlg_fpfh_knn", "dlg_sac_ia_score", "dlg_sac_ia_align",
     "dlg_debug_live_bytes",
+    "dlg_gs_params_default", "dlg_gs_space", "dlg_gs_vote", "dlg_gs_segment",
+    "dlg_cloud_gs_segment",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -195,6 +197,33 @@ class SacIaStats(C.Structure):
                 ("relaxations", C.c_int64), ("n_queries", C.c_int64), ("host_syncs", C.c_int64),
                 ("error", C.c_double), ("fitness", C.c_double), ("build_ms", C.c_double),
                 ("knn_ms", C.c_double), ("score_ms", C.c_double), ("device_ms", C.c_double)]
+
+
+class GsParams(C.Structure):
+    _fields_ = [("num_res", C.c_float), ("std_dev_gaussian", C.c_float),
+                ("search_radius_create_gradient", C.c_float), ("t_vote_num", C.c_int32),
+                ("radius_base", C.c_float), ("delta_radius", C.c_float),
+                ("s_threshold", C.c_float), ("dev_threshold", C.c_float),
+                ("search_radius_for_plane_seg", C.c_float), ("t_num_of_single_plane", C.c_int32)]
+
+
+class GsStats(C.Structure):
+    _fields_ = [("n_cells", C.c_int64), ("n_occupied", C.c_int64), ("n_voters", C.c_int64),
+                ("n_fallback_votes", C.c_int64), ("n_filter_pairs", C.c_int64),
+                ("n_sinks", C.c_int64), ("n_planes", C.c_int64), ("n_plane_points", C.c_int64),
+                ("space_ms", C.c_double), ("vote_ms", C.c_double), ("filter_ms", C.c_double),
+                ("segment_ms", C.c_double), ("host_ms", C.c_double), ("device_ms", C.c_double)]
+
+
+class GsResult(C.Structure):
+    _fields_ = [("plane_offsets", C.POINTER(C.c_int64)), ("planes_cap", C.c_int64),
+                ("plane_ids", C.POINTER(C.c_int32)), ("ids_cap", C.c_int64),
+                ("sink_cells", C.POINTER(C.c_int32)), ("sink_votes", C.POINTER(C.c_int64)),
+                ("sinks_cap", C.c_int64), ("cell_of_point", C.POINTER(C.c_int32)),
+                ("raw_vote", C.POINTER(C.c_int32)), ("filtered_vote", C.POINTER(C.c_int32)),
+                ("sink_init", C.POINTER(C.c_int32)), ("sink", C.POINTER(C.c_int32)),
+                ("cells_cap", C.c_int64), ("n_planes", C.c_int64), ("n_ids", C.c_int64),
+                ("n_sinks", C.c_int64), ("n_cells", C.c_int64)]
 
 
 class SacParams(C.Structure):
@@ -358,10 +387,20 @@ def load():
     L.dlg_sac_ia_align.argtypes = [vp, C.POINTER(Points), fp, C.c_int64, C.POINTER(Points), fp,
                                    C.c_int64, C.POINTER(SacIaParams), fp, fp, fp, C.c_int64,
                                    C.POINTER(SacIaHypothesis), C.c_int64, C.POINTER(SacIaStats)]
+    L.dlg_gs_params_default.argtypes = [C.POINTER(GsParams)]
+    L.dlg_gs_params_default.restype = None
+    L.dlg_gs_space.argtypes = [C.POINTER(GsParams), fp, C.c_int64, i64p]
+    L.dlg_gs_vote.argtypes = [vp, fp, C.c_int64, C.c_int64, C.POINTER(GsParams), i32p, i32p,
+                              C.c_int64, C.POINTER(GsStats)]
+    L.dlg_gs_segment.argtypes = [vp, C.POINTER(Points), fp, C.c_int64, C.POINTER(GsParams),
+                                 C.POINTER(GsResult), C.POINTER(GsStats)]
+    L.dlg_cloud_gs_segment.argtypes = [vp, vp, C.POINTER(GsParams), C.POINTER(GsResult),
+                                       C.POINTER(GsStats)]
     for s in SYMBOLS:
         if s not in ("dlg_abi_version", "dlg_status_string", "dlg_sac_params_default",
                      "dlg_last_error", "dlg_abi_struct_size", "dlg_icp_params_default",
-                     "dlg_sac_ia_params_default", "dlg_debug_live_bytes"):
+                     "dlg_sac_ia_params_default", "dlg_debug_live_bytes",
+                     "dlg_gs_params_default"):
             getattr(L, s).restype = C.c_int
     _lib = L
     return L

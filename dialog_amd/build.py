@@ -18,7 +18,8 @@ LIB = os.path.join(HERE, "libdialog_amd.so")
 SOURCES = ["kernels.hip", "fsum.hip", "spatial.hip", "normals.hip", "postprocess.hip", "comm.cpp", "cloud_call.cpp", "driver.cpp", "segment.cpp", "sac_control.cpp",
            "normals_host.cpp", "postprocess_host.cpp", "voxel.hip", "voxel_host.cpp",
            "sor.hip", "sor_host.cpp", "mls.hip", "mls_host.cpp", "icp.hip", "icp_host.cpp",
-           "fpfh.hip", "fpfh_host.cpp", "sacia.hip", "sacia_host.cpp"]
+           "fpfh.hip", "fpfh_host.cpp", "sacia.hip", "sacia_host.cpp", "gsphere.hip",
+           "gsphere_host.cpp"]
 # every header under csrc/ (a header change rebuilds every object: no per-file dependency scan)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp") or f.endswith(".h"))
 ARCH = os.environ.get("DLG_OFFLOAD_ARCH", "gfx950")

@@ -167,6 +167,10 @@ int64_t dlg_abi_struct_size(int which) {
     case 19: return (int64_t)sizeof(dlg_sac_ia_params);
     case 20: return (int64_t)sizeof(dlg_sac_ia_hypothesis);
     case 21: return (int64_t)sizeof(dlg_sac_ia_stats);
+    // (22 is left unassigned)
+    case 23: return (int64_t)sizeof(dlg_gs_params);
+    case 24: return (int64_t)sizeof(dlg_gs_stats);
+    case 25: return (int64_t)sizeof(dlg_gs_result);
   }
   return -1;
 }

@@ -19,6 +19,7 @@
 #include "../../include/dialog_ransac.h"
 #include "call_args.hpp"
 #include "comm.hpp"
+#include "gsphere_model.hpp"
 #include "kernels.hpp"
 #include "sac_control.hpp"
 #include "postprocess.hpp"
@@ -227,6 +228,22 @@ struct SaciaWork {
   DevBuf<unsigned long long> qa, qb, acc;
 };
 
+// scratch of the Gaussian-sphere plane seeds (gsphere_host.cpp; the points and their grid are the
+// shared nw.x/y/z and nw.lv[0], the normals nw.nrm).  The parameter space of the last num_res is
+// kept, on the host and on the device.
+struct GsWork {
+  gs::Space space;
+  DevBuf<int32_t> table, coord;
+  DevBuf<float> px, py, pz;
+  DevBuf<int32_t> cell_of, votes, filt, queue, sink, sink_rank, label, lab_s, parent, root_of;
+  DevBuf<int32_t> ids, ids_a, ids_b, first, offs, n_planes;
+  DevBuf<uint32_t> reach, off, cur, size, total, key2, key2_out;
+  DevBuf<uint64_t> keys, key1, key1_out;
+  DevBuf<float> terms;
+  DevBuf<uint8_t> heads, tmp;
+  DevBuf<unsigned long long> cnt;
+};
+
 }  // namespace dlg
 
 using namespace dlg;
@@ -394,6 +411,7 @@ struct dlg_ctx {
   IcpWork iw;
   FpfhWork fw;
   SaciaWork aw;
+  GsWork gw;
   // PCL float refit on the device (fsum.hip): scratch sized for fs_cap inliers
   DevBuf<uint8_t> fs_scr;
   // the spatial index build's sort scratch (Morton keys and orders, ping-pong; radix-sort

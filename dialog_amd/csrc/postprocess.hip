@@ -24,6 +24,7 @@
 
 #include "grid_dev.hpp"
 #include "postprocess.hpp"
+#include "union_find_dev.hpp"
 
 namespace dlg {
 
@@ -278,36 +279,7 @@ __global__ __launch_bounds__(kBS) void k_xyz_lookup(
 }
 
 // ---- clusterFilt: union-find over sorted positions ----
-__device__ __forceinline__ int uf_load(int32_t* parent, int x) {
-  return __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of x with path halving (benign races: every stored value is an ancestor)
-__device__ int uf_find(int32_t* parent, int x) {
-  int p = uf_load(parent, x);
-  while (p != x) {
-    const int g = uf_load(parent, p);
-    if (g != p)
-      __hip_atomic_store(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = p;
-    p = g;
-  }
-  return x;
-}
-
-__device__ void uf_unite(int32_t* parent, int a, int b) {
-  while (true) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    // hook the larger root under the smaller; a failed CAS means a was hooked meanwhile
-    const int old = atomicCAS(&parent[a], a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
+// (uf_find, uf_unite: union_find_dev.hpp)
 __global__ __launch_bounds__(kBS) void k_cc_init(int32_t* __restrict__ parent,
                                                  uint32_t* __restrict__ size, int n) {
   const int u = blockIdx.x * kBS + threadIdx.x;

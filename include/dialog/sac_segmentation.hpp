@@ -1081,6 +1081,50 @@ inline size_t fillPlaneClouds(const pcl::PointCloud<PointT>& cloud,
   return added;
 }
 
+// createPS() ... segmentPlanes() (PlaneDetect.h:667-1005) on dlg_gs_segment: the reference's own
+// detector up to its seed planes.  Appends one PlaneT per seed plane to plane_clouds with
+// points_set alone filled, as segmentPlanes leaves it (border null, coeff empty: growPlaneArea
+// sets those), in the reference's plane order; each plane holds its distinct points.  PointNT needs
+// normal_x / normal_y / normal_z first in its record (pcl::Normal).  prm: dlg_gs_params_default()
+// gives the config.txt values.  Returns the number of planes added.
+template <typename PointT, typename PointNT, typename PlaneT, typename Alloc>
+inline size_t segmentPlanesGaussSphere(const pcl::PointCloud<PointT>& cloud,
+                                       const pcl::PointCloud<PointNT>& normals,
+                                       const dlg_gs_params& prm,
+                                       std::vector<PlaneT, Alloc>& plane_clouds,
+                                       Context* ctx = nullptr, dlg_gs_stats* stats = nullptr) {
+  if (normals.points.size() != cloud.points.size())
+    throw Error(DLG_ERR_INVALID, "segmentPlanesGaussSphere: one normal per cloud point");
+  const int64_t n = (int64_t)cloud.points.size();
+  if (n == 0) return 0;
+  dlg_ctx* c = (ctx ? ctx : &Context::thread_default())->get();
+  dlg_points pts{&cloud.points[0].x, n, (int64_t)sizeof(PointT)};
+  std::vector<int64_t> off((size_t)n + 1), votes(64);
+  std::vector<int32_t> ids((size_t)n), cells(64);
+  dlg_gs_result r = dlg_gs_result();
+  dlg_status st;
+  for (;;) {
+    r.plane_offsets = off.data(); r.planes_cap = n;
+    r.plane_ids = ids.data(); r.ids_cap = n;
+    r.sink_cells = cells.data(); r.sink_votes = votes.data(); r.sinks_cap = (int64_t)cells.size();
+    st = dlg_gs_segment(c, &pts, &normals.points[0].normal_x, (int64_t)sizeof(PointNT), &prm, &r,
+                        stats);
+    if (st != DLG_ERR_CAPACITY || r.n_sinks <= (int64_t)cells.size()) break;
+    cells.resize((size_t)r.n_sinks);
+    votes.resize((size_t)r.n_sinks);
+  }
+  check(st, c);
+  for (int64_t k = 0; k < r.n_planes; ++k) {
+    PlaneT pl;
+    pl.points_set.reset(new pcl::PointCloud<PointT>);
+    pl.points_set->points.reserve((size_t)(off[(size_t)k + 1] - off[(size_t)k]));
+    for (int64_t j = off[(size_t)k]; j < off[(size_t)k + 1]; ++j)
+      pl.points_set->push_back(cloud.points[(size_t)ids[(size_t)j]]);
+    plane_clouds.push_back(std::move(pl));
+  }
+  return (size_t)r.n_planes;
+}
+
 // polyPointCloud() (PlaneDetect.h:1376-1440) on dlg_plane_border: the plane's points projected
 // onto their least-squares plane (pcl::computePointNormal + projPoint2Plane), the concave border
 // of pcl::ConcaveHull (alpha shape of the projected points, alpha = alpha_poly, config.txt:28;

@@ -60,7 +60,8 @@ extern "C" {
  * dlg_fpfh_stats (same ABI version: added entries); dlg_sac_ia_align, dlg_sac_ia_score,
  * dlg_fpfh_knn, dlg_sac_ia_params_default, dlg_sac_ia_params, dlg_sac_ia_hypothesis,
  * dlg_sac_ia_stats (same ABI version: added entries); DLG_OPT_CULL_FUSE (same ABI version: an added
- * option) */
+ * option); dlg_gs_params_default, dlg_gs_space, dlg_gs_vote, dlg_gs_segment, dlg_cloud_gs_segment,
+ * dlg_gs_params, dlg_gs_stats, dlg_gs_result (same ABI version: added entries) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -171,8 +172,8 @@ int dlg_abi_version(void);
  * 2 dlg_sac_stats, 3 dlg_extract_stats, 4 dlg_planes, 5 dlg_postprocess_params, 6 dlg_voxel_params,
  * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats, 10 dlg_mls_params, 11 dlg_mls_stats,
  * 13 dlg_icp_params, 14 dlg_icp_stats, 15 dlg_icp_iteration, 17 dlg_fpfh_params, 18 dlg_fpfh_stats,
- * 19 dlg_sac_ia_params, 20 dlg_sac_ia_hypothesis, 21 dlg_sac_ia_stats (12 and 16 are unassigned);
- * -1 otherwise */
+ * 19 dlg_sac_ia_params, 20 dlg_sac_ia_hypothesis, 21 dlg_sac_ia_stats, 23 dlg_gs_params,
+ * 24 dlg_gs_stats, 25 dlg_gs_result (12, 16 and 22 are unassigned); -1 otherwise */
 int64_t dlg_abi_struct_size(int which);
 
 /* ---- contexts ------------------------------------------------------------------------------ */
@@ -805,6 +806,103 @@ dlg_status dlg_sac_ia_align(dlg_ctx* ctx, const dlg_points* src, const float* sr
                             float* aligned_out, int64_t out_stride_bytes,
                             dlg_sac_ia_hypothesis* hyp_out, int64_t hyp_cap,
                             dlg_sac_ia_stats* stats);
+
+/* ---- Gaussian-sphere plane seeds (Dialog/PlaneDetect.h:667-1015) ----------------------------- */
+/* The reference's plane detector up to the seed planes: createPS -> voteForPS -> filtPS ->
+ * createGradientField -> rectifySinkFields -> segmentPlanes (called from PCLViewer.cpp:887-960 and
+ * :1133-1151); growPlaneArea and mergePlanes are not part of it.
+ *   parameter space (PS): the lattice cubes of edge num_res in [-1, 1)^3 (floor(2 / num_res + 0.5)
+ *   per axis) whose 8 float corner norms straddle 1; the PS index is the enumeration order, x
+ *   outer, z inner; a cell's point is its min corner (float)i * num_res - 1.
+ *   vote: per point the query floor(n / num_res) * num_res per component; the vote goes to the PS
+ *   cell of the smallest (FLANN float d2, index) over all cells.  A point whose normal has a
+ *   non-finite component casts no vote (cell -1).
+ *   filter: per PS cell, over the cells with d2 < (float)((double)r * r), r = (float)(3.0 *
+ *   std_dev_gaussian), in (d2, index) order, G += (float)(C / A) * (float)vote as a sequential
+ *   float sum (A, C in double with the reference's float PI and e, d = sqrtf(d2)); the new vote is
+ *   (int)floor(G + 0.5f).
+ *   gradient field, sinks: on the host over the filtered votes, by the reference's rules; vote_num
+ *   sums raw votes; a sink is kept iff vote_num > t_vote_num.  The rectification's sine is the
+ *   double sine rounded to float.
+ *   seed planes: a point with finite coordinates carries its cell's sink; per sink with at least
+ *   t_num_of_single_plane points, the connected components of the radius graph
+ *   (search_radius_for_plane_seg) of its points.  The reference's BFS pushes every point of a
+ *   component but its seed twice before it tests the size, so a component of m points is kept iff
+ *   2 m - 1 >= t_num_of_single_plane.  A plane is returned as its distinct cloud indices.  Order:
+ *   sinks as found; within a sink its points listed by (PS cell, point index), the components by
+ *   their first point in that list, the indices of a plane in list order.
+ * DLG_ERR_INVALID: a num_res that is not finite, not > 0, or gives more than 512 lattice cells per
+ * axis; a std_dev_gaussian or a radius that is not finite and > 0; a delta_radius that does not
+ * end the rectification within 100000 steps; negative thresholds; n above INT32_MAX / 2; a
+ * context of a communicator with world > 1 (one rank's shard lacks the votes and the neighbours
+ * of the others). */
+typedef struct {
+  float num_res;                        /* config.txt: 0.01 */
+  float std_dev_gaussian;               /* 0.05 */
+  float search_radius_create_gradient;  /* 0.03 */
+  int32_t t_vote_num;                   /* 500 */
+  float radius_base;                    /* 0.03 */
+  float delta_radius;                   /* 0.01 */
+  float s_threshold;                    /* 0.9 */
+  float dev_threshold;                  /* 15.0 (degrees) */
+  float search_radius_for_plane_seg;    /* 0.1 */
+  int32_t t_num_of_single_plane;        /* 500 */
+} dlg_gs_params;                        /* dlg_abi_struct_size(23) */
+
+typedef struct {
+  int64_t n_cells;           /* PS cells */
+  int64_t n_occupied;        /* PS cells with a raw vote */
+  int64_t n_voters;          /* points that cast a vote */
+  int64_t n_fallback_votes;  /* of them, by the search of all cells (the box bound failed) */
+  int64_t n_filter_pairs;    /* (PS cell, occupied cell within the radius) pairs of the filter */
+  int64_t n_sinks;           /* kept sinks */
+  int64_t n_planes;
+  int64_t n_plane_points;
+  double space_ms;           /* host: the parameter space built and uploaded (0 when kept) */
+  double vote_ms, filter_ms, segment_ms;  /* profiling: HIP events around the three device phases */
+  double host_ms;            /* host: gradient field and sink rectification */
+  double device_ms;          /* vote_ms + filter_ms + segment_ms */
+} dlg_gs_stats;              /* dlg_abi_struct_size(24) */
+
+/* caller buffers of dlg_gs_segment and the sizes it found (set on DLG_ERR_CAPACITY too, when
+ * nothing is written to the buffer that is too small) */
+typedef struct {
+  int64_t* plane_offsets;  /* planes_cap + 1: plane k owns plane_ids[offsets[k] .. offsets[k + 1]) */
+  int64_t planes_cap;
+  int32_t* plane_ids;      /* ids_cap cloud indices */
+  int64_t ids_cap;
+  int32_t* sink_cells;     /* sinks_cap: the kept sinks' PS index, in order */
+  int64_t* sink_votes;     /* sinks_cap: their vote_num */
+  int64_t sinks_cap;
+  int32_t* cell_of_point;  /* nullable, n: the PS cell each point voted for, -1 none */
+  int32_t* raw_vote;       /* nullable, n_cells each: voteForPS's count, */
+  int32_t* filtered_vote;  /*   filtPS's vote, */
+  int32_t* sink_init;      /*   createGradientField's and */
+  int32_t* sink;           /*   rectifySinkFields' sink per cell */
+  int64_t cells_cap;       /* entries of each of the four (>= n_cells when any is given) */
+  int64_t n_planes, n_ids, n_sinks, n_cells;  /* out */
+} dlg_gs_result;           /* dlg_abi_struct_size(25) */
+
+void dlg_gs_params_default(dlg_gs_params* p);  /* the config.txt values above */
+/* createPS on the host (no context): *n_cells, and with corners_out (cap rows of 3 floats) every
+ * cell's min corner in PS order; DLG_ERR_CAPACITY (with *n_cells) when cap is too small. */
+dlg_status dlg_gs_space(const dlg_gs_params* params, float* corners_out, int64_t cap,
+                        int64_t* n_cells);
+/* voteForPS alone: normals are n records of stride_bytes (>= 12, a multiple of 4; x, y, z first);
+ * cell_of_point: n entries; votes (nullable): votes_cap >= n_cells entries.  stats (nullable):
+ * n_cells, n_occupied, n_voters, n_fallback_votes, vote_ms. */
+dlg_status dlg_gs_vote(dlg_ctx* ctx, const float* normals, int64_t n, int64_t stride_bytes,
+                       const dlg_gs_params* params, int32_t* cell_of_point, int32_t* votes,
+                       int64_t votes_cap, dlg_gs_stats* stats);
+dlg_status dlg_gs_segment(dlg_ctx* ctx, const dlg_points* pts, const float* normals,
+                          int64_t normals_stride_bytes, const dlg_gs_params* params,
+                          dlg_gs_result* result, dlg_gs_stats* stats);
+/* The same over a cloud's own device copy (every uploaded point, upload order) and its attached
+ * normals as given (dlg_cloud_set_normals, dlg_cloud_estimate_normals, flipped by
+ * dlg_cloud_regulate_normals): normals -> RegulateNormal -> seeds has no host round trip on the
+ * input side.  DLG_ERR_INVALID when no normals are attached. */
+dlg_status dlg_cloud_gs_segment(dlg_ctx* ctx, dlg_cloud* cloud, const dlg_gs_params* params,
+                                dlg_gs_result* result, dlg_gs_stats* stats);
 
 /* ---- postProcessPlanes (Dialog/PlaneDetect.h:1454-1579) ------------------------------------ */
 /* The final planes (plane_clouds_final, HeaderFile.h:98; struct Plane HeaderFile.h:81-88) as
