@@ -46,7 +46,7 @@ SYMBOLS = [
     "dlg_sac_ia_params_default", "dlg_fpfh_knn", "dlg_sac_ia_score", "dlg_sac_ia_align",
     "dlg_debug_live_bytes",
     "dlg_gs_params_default", "dlg_gs_space", "dlg_gs_vote", "dlg_gs_segment",
-    "dlg_cloud_gs_segment",
+    "dlg_cloud_gs_segment", "dlg_knn_stats",
 ]
 
 # context options (include/dialog_ransac.h): equivalent execution paths, identical results
@@ -226,6 +226,12 @@ class GsResult(C.Structure):
                 ("n_sinks", C.c_int64), ("n_cells", C.c_int64)]
 
 
+class KnnRecord(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("k", C.c_int32), ("n", C.c_int64),
+                ("levels_planned", C.c_int32), ("reserved", C.c_int32),
+                ("queries", C.c_int64 * 12), ("built", C.c_int32 * 12)]
+
+
 class SacParams(C.Structure):
     _fields_ = [("threshold", C.c_double), ("max_iterations", C.c_int), ("probability", C.c_double),
                 ("optimize", C.c_int), ("seed", C.c_uint32), ("model", C.c_int),
@@ -314,6 +320,7 @@ def load():
     L.dlg_ctx_get_option.argtypes = [vp, C.c_int, i64p]
     L.dlg_prune_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.dlg_cull_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+    L.dlg_knn_stats.argtypes = [vp, C.POINTER(KnnRecord)]
     L.dlg_preprocess.argtypes = [vp, C.POINTER(Points), C.c_int, C.c_float, fp, C.c_int64, i32p,
                                  C.c_int64, i64p, fp]
     L.dlg_orient_normals_nn.argtypes = [vp, C.POINTER(Points), fp, C.c_int64, C.POINTER(Points),

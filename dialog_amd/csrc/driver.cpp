@@ -171,6 +171,7 @@ int64_t dlg_abi_struct_size(int which) {
     case 23: return (int64_t)sizeof(dlg_gs_params);
     case 24: return (int64_t)sizeof(dlg_gs_stats);
     case 25: return (int64_t)sizeof(dlg_gs_result);
+    case 26: return (int64_t)sizeof(dlg_knn_record);
   }
   return -1;
 }
@@ -883,6 +884,12 @@ dlg_status dlg_cull_stats(dlg_ctx* c, uint64_t out[8], int reset) {
     if (reset) HIPCHK(hipMemsetAsync(st, 0, kCullStats * sizeof(unsigned long long), c->stream));
     sync(c);
   });
+}
+
+dlg_status dlg_knn_stats(dlg_ctx* c, dlg_knn_record* out) {
+  if (!c || !out) return DLG_ERR_INVALID;
+  *out = c->knn_rec;  // (host bookkeeping of normals_core's level loop: nothing to read back)
+  return DLG_OK;
 }
 
 dlg_status dlg_set_profiling(dlg_ctx* c, int enable) {

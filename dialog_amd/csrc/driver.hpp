@@ -404,6 +404,7 @@ struct dlg_ctx {
   int32_t* emit_dst = nullptr;  // a round's inliers to copy (enqueued after the next launches)
   int64_t emit_n = 0;
   NormalsWork nw;
+  dlg_knn_record knn_rec = {};  // dlg_knn_stats: the levels the last k-NN normals call used
   PostWork pw;
   VoxelWork vw;
   SorWork sw;

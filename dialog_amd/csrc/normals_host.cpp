@@ -279,8 +279,15 @@ void normals_core(dlg_ctx* c, int n, const BBox& b, float radius, int k_nn, cons
       }
     }
   } else {
+    // dlg_knn_stats' record: invalid while the call runs, filled from the level loop below
+    dlg_knn_record& rec = c->knn_rec;
+    rec = dlg_knn_record{};
+    static_assert(sizeof(rec.queries) / sizeof(rec.queries[0]) == kMaxLevels, "dlg_knn_record");
     KnnPlan plan;
     KnnLevels L = build_hierarchy_plan(c, n, b, k_nn, &plan, 1);
+    rec.k = k_nn;
+    rec.n = n;
+    rec.levels_planned = L.levels;
     w.queue.ensure(n);
     w.processed.ensure(n);
     // deferred-query flags per level, indexed by point: a level is built only once some query
@@ -322,9 +329,13 @@ void normals_core(dlg_ctx* c, int n, const BBox& b, float radius, int k_nn, cons
         nq = count_flags(w.processed.p);
         qpos = w.queue.p;
       }
+      rec.queries[l] = nq;
       launch_normals_knn(L, l, qpos, nq, w.x.p, w.y.p, w.z.p, k_nn, vp, w.nrm.p, w.dflags.p,
                          (int64_t)n, L.levels - 1, pclf, c->stream, tnext);
     }
+    HIPCHK(hipGetLastError());
+    for (int l = 0; l < L.levels; ++l) rec.built[l] = built[l] ? 1 : 0;
+    rec.valid = 1;
   }
   HIPCHK(hipGetLastError());
 }

@@ -151,6 +151,17 @@ class Context:
         return {"rounds": a[0], "scored_a": a[1], "scored_b": a[2], "culled": a[3],
                 "rounds_with_b": a[4], "fallbacks": a[5]}
 
+    def knn_stats(self) -> dict:
+        """dlg_knn_stats: the grid levels this context's most recent k-NN normals call used
+        (host bookkeeping; a radius call leaves it alone).  valid is False until one has run;
+        queries[l] / built[l] are per level, levels_planned long."""
+        r = _lib.KnnRecord()
+        self.check(self._L.dlg_knn_stats(self.h, C.byref(r)))
+        m = int(r.levels_planned)
+        return {"valid": bool(r.valid), "k": int(r.k), "n": int(r.n), "levels_planned": m,
+                "queries": [int(v) for v in r.queries[:m]],
+                "built": [int(v) for v in r.built[:m]]}
+
     def set_profiling(self, on=True):
         """on: True / 1 = all timing events, 2 = without the PCL refit walk's, False / 0 = none."""
         self.check(self._L.dlg_set_profiling(self.h, int(on)))

@@ -61,7 +61,8 @@ extern "C" {
  * dlg_fpfh_knn, dlg_sac_ia_params_default, dlg_sac_ia_params, dlg_sac_ia_hypothesis,
  * dlg_sac_ia_stats (same ABI version: added entries); DLG_OPT_CULL_FUSE (same ABI version: an added
  * option); dlg_gs_params_default, dlg_gs_space, dlg_gs_vote, dlg_gs_segment, dlg_cloud_gs_segment,
- * dlg_gs_params, dlg_gs_stats, dlg_gs_result (same ABI version: added entries) */
+ * dlg_gs_params, dlg_gs_stats, dlg_gs_result (same ABI version: added entries); dlg_knn_stats,
+ * dlg_knn_record (same ABI version: an added entry) */
 #define DLG_ABI_VERSION 5
 
 typedef enum {
@@ -173,7 +174,7 @@ int dlg_abi_version(void);
  * 7 dlg_voxel_stats, 8 dlg_sor_params, 9 dlg_sor_stats, 10 dlg_mls_params, 11 dlg_mls_stats,
  * 13 dlg_icp_params, 14 dlg_icp_stats, 15 dlg_icp_iteration, 17 dlg_fpfh_params, 18 dlg_fpfh_stats,
  * 19 dlg_sac_ia_params, 20 dlg_sac_ia_hypothesis, 21 dlg_sac_ia_stats, 23 dlg_gs_params,
- * 24 dlg_gs_stats, 25 dlg_gs_result (12, 16 and 22 are unassigned); -1 otherwise */
+ * 24 dlg_gs_stats, 25 dlg_gs_result, 26 dlg_knn_record (12, 16 and 22 are unassigned); -1 otherwise */
 int64_t dlg_abi_struct_size(int which);
 
 /* ---- contexts ------------------------------------------------------------------------------ */
@@ -1240,6 +1241,25 @@ dlg_status dlg_prune_stats(dlg_ctx* ctx, uint64_t out[8], int reset);
  * [5] rounds that scored more than 1/16 of their batch (culling then stops for the call); [6], [7] 0.
  * dlg_score_benchmark's ids do not count */
 dlg_status dlg_cull_stats(dlg_ctx* ctx, uint64_t out[8], int reset);
+
+/* Which levels of the grid hierarchy the context's most recent k-NN normals call used
+ * (dlg_estimate_normals[_ex] or dlg_cloud_estimate_normals with k_nn > 0).  Host bookkeeping of
+ * the call's level loop: no device counters, nothing is read from the device.  A radius call
+ * (k_nn == 0) leaves the record alone; a k-NN call clears `valid` when it starts and sets it when
+ * its last level is launched, so a call that fails before that leaves valid == 0.  A call refused
+ * for its arguments and an empty cloud (n == 0) run no search and leave the record alone. */
+typedef struct {
+  int32_t valid;           /* 0 until the context has finished a k-NN normals call */
+  int32_t k;               /* the call's k_nn */
+  int64_t n;               /* points of the call (non-finite rows included) */
+  int32_t levels_planned;  /* levels of the hierarchy's plan (1..12); 1: the plain per-thread
+                              search, no deferral */
+  int32_t reserved;        /* 0 */
+  int64_t queries[12];     /* queries launched at level l ([0] == n); 0 beyond levels_planned */
+  int32_t built[12];       /* 1: level l's grid was built ([0] always; a coarser level only once
+                              some query was deferred to it) */
+} dlg_knn_record;          /* dlg_abi_struct_size(26) */
+dlg_status dlg_knn_stats(dlg_ctx* ctx, dlg_knn_record* out);
 
 /* The shard of an n_global-point cloud rank `rank` of `world` should upload:
  * the contiguous range [*lo, *hi) of the global order, or -- when a shard would fall below the

@@ -872,7 +872,8 @@ void orc_estimate_normals(const float* xyz, int64_t n, int64_t stride, float rad
 
 /* k-nearest-neighbour variant: NormalEstimation with setKSearch(k) (PCLViewer.cpp:507-522,
  * TriangularMeshing.h:28-35, k = 20).  Neighbours = the k smallest (dist2, index) pairs, FLANN's
- * sorted kNN result (the query itself has dist2 0), NaN distances never taken.  The brute-force
+ * sorted kNN result (the query itself has dist2 0), rows with a NaN or infinite coordinate never
+ * taken and NaN as queries (pcl::isFinite, see orc_estimate_normals_knn_brute).  The brute-force
  * form is the definition; the grid form below finds the same pairs (checked against it on
  * tie-heavy clouds, tests/test_oracle.py) and is what clouds of any size use when every
  * coordinate is finite. */
@@ -893,27 +894,43 @@ void orc_estimate_normals_knn_brute(const float* xyz, int64_t n, int64_t stride,
                                     const float vp[3], float* out) {
   orc_nb* all = (orc_nb*)malloc((size_t)(n > 0 ? n : 1) * sizeof(orc_nb));
   int32_t* ids = (int32_t*)malloc((size_t)(k_nn > 0 ? k_nn : 1) * sizeof(int32_t));
+  /* PCL's rule for a non-dense cloud (PCL 1.8, restated from memory like the rest of this file):
+   * pcl::isFinite(point) -- every coordinate finite, so +-inf as well as NaN -- decides both
+   * sides.  NormalEstimation::computeFeature gives a query that fails
+   * it a NaN normal (normal_3d.hpp), and KdTreeFLANN::convertCloudToArray leaves such points out of
+   * the tree (kdtree_flann.hpp), so they are nobody's neighbour.  The test is on the row's
+   * coordinates, not on d: a d2 that overflows to +inf between two finite points stays a
+   * candidate. */
+  uint8_t* fin = (uint8_t*)malloc((size_t)(n > 0 ? n : 1));
+  for (int64_t j = 0; j < n; ++j) {
+    const float* q = xyz + j * stride;
+    fin[j] = (uint8_t)(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]));
+  }
   for (int64_t i = 0; i < n; ++i) {
     const float* p = xyz + i * stride;
     float* o = out + 4 * i;
+    if (!fin[i]) {
+      o[0] = o[1] = o[2] = o[3] = NAN;
+      continue;
+    }
     int64_t m = 0;
     for (int64_t j = 0; j < n; ++j) {
+      if (!fin[j]) continue;
       const float* q = xyz + j * stride;
       float ex = p[0] - q[0], ey = p[1] - q[1], ez = p[2] - q[2];
       float d = ((0.0f + ex * ex) + ey * ey) + ez * ez;
-      if (d != d) continue;
       all[m].d = d; all[m].j = (int32_t)j; ++m;
     }
     qsort(all, (size_t)m, sizeof(orc_nb), orc_nb_cmp);
     int64_t k = m < k_nn ? m : k_nn;
-    if (k < 3 || !(p[0] == p[0] && p[1] == p[1] && p[2] == p[2])) {
+    if (k < 3) {
       o[0] = o[1] = o[2] = o[3] = NAN;
       continue;
     }
     for (int64_t t = 0; t < k; ++t) ids[t] = all[t].j;
     orc_normal_from_ids(xyz, stride, p, ids, k, vp, o);
   }
-  free(all); free(ids);
+  free(all); free(ids); free(fin);
 }
 
 /* (d, j) lexicographic: a before b */

@@ -70,10 +70,26 @@ def test_struct_layouts_match_the_header():
     binding built for another layout would read or write past the caller's struct."""
     L = _lib.load()
     pairs = [(0, _lib.Points), (1, _lib.SacParams), (2, _lib.SacStats), (3, _lib.ExtractStats),
-             (4, _lib.Planes), (5, _lib.PostProcessParams)]
+             (4, _lib.Planes), (5, _lib.PostProcessParams), (26, _lib.KnnRecord)]
     for which, cls in pairs:
         assert L.dlg_abi_struct_size(which) == C.sizeof(cls), cls.__name__
     assert L.dlg_abi_struct_size(99) == -1
+    assert L.dlg_abi_struct_size(27) == -1
+
+
+def test_knn_stats_is_exported():
+    """dlg_knn_stats / dlg_knn_record: an added entry under the same ABI version; the record is
+    168 bytes (12 levels) and the call refuses null arguments without a context"""
+    L = _lib.load()
+    assert "dlg_knn_stats" in _lib.SYMBOLS and hasattr(L, "dlg_knn_stats")
+    assert hasattr(dialog_amd.Context, "knn_stats")
+    assert L.dlg_abi_struct_size(26) == C.sizeof(_lib.KnnRecord) == 168
+    assert [f[0] for f in _lib.KnnRecord._fields_] == ["valid", "k", "n", "levels_planned",
+                                                       "reserved", "queries", "built"]
+    assert len(_lib.KnnRecord().queries) == len(_lib.KnnRecord().built) == 12
+    r = _lib.KnnRecord()
+    assert L.dlg_knn_stats(None, C.byref(r)) == _lib.DLG_ERR_INVALID
+    assert L.dlg_abi_version() == _lib.ABI_VERSION == 5
 
 
 def test_no_device_fails_loudly(monkeypatch):

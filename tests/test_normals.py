@@ -17,8 +17,8 @@ import os
 
 import numpy as np
 import pytest
-from scipy.spatial import cKDTree
 
+from normals_ref import angle, f64_normals, flann_radius_sets, knn_sets
 from oracle import oracle as O
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -29,63 +29,6 @@ RADIUS = 0.1
 def small_cloud(n=12000, seed=7, planes=3, patch=2.0, outliers=0.05):
     from dialog_amd.synth import plane_cloud
     return plane_cloud(n, planes, outlier_frac=outliers, seed=seed, patch=patch)
-
-
-def flann_radius_sets(p, r):
-    """exact KdTreeFLANN radius sets: float d2 = ((0 + dx^2) + dy^2) + dz^2 < float(r*r)."""
-    r2 = np.float32(float(r) * float(r))
-    tree = cKDTree(p.astype(np.float64))
-    cand = tree.query_ball_point(p.astype(np.float64), r * 1.001)
-    out = []
-    for i, c in enumerate(cand):
-        c = np.asarray(c, np.int64)
-        d = p[i][None, :] - p[c]
-        d2 = ((np.float32(0) + d[:, 0] * d[:, 0]) + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-        out.append(np.sort(c[d2 < r2]))
-    return out
-
-
-def knn_sets(p, k):
-    """FLANN kNN sets: the k smallest (float d2, index) among the points (query included)."""
-    tree = cKDTree(p.astype(np.float64))
-    _, cand = tree.query(p.astype(np.float64), k=min(k + 8, len(p)))
-    out = []
-    for i, c in enumerate(cand):
-        d = p[i][None, :] - p[c]
-        d2 = ((np.float32(0) + d[:, 0] * d[:, 0]) + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-        o = np.lexsort((c, d2))[:k]
-        out.append(np.sort(c[o]))
-    return out
-
-
-def f64_normals(p, sets, vp=(0.0, 0.0, 0.0)):
-    """float64 restatement: covariance, eigh, curvature, viewpoint flip; + eigen-gap quality."""
-    n = p.shape[0]
-    out = np.full((n, 4), np.nan)
-    gap = np.zeros(n)
-    P = p.astype(np.float64)
-    for i, s in enumerate(sets):
-        if len(s) < 3:
-            continue
-        q = P[s]
-        c = np.cov(q.T, bias=True)
-        w, v = np.linalg.eigh(c)
-        nv = v[:, 0]
-        if np.dot(np.asarray(vp) - P[i], nv) < 0:
-            nv = -nv
-        tr = w.sum()
-        out[i, :3] = nv
-        out[i, 3] = abs(w[0] / tr) if tr != 0 else 0.0
-        gap[i] = (w[1] - w[0]) / max(w[2], 1e-300)
-    return out, gap
-
-
-def angle(a, b):
-    """unsigned angle between the lines of two normal sets, robust near 0 (float32 unit vectors
-    are only unit to ~6e-8, which arccos of the dot product would turn into ~3e-4 rad)."""
-    a = a[:, :3].astype(np.float64)
-    b = b[:, :3].astype(np.float64)
-    return np.arctan2(np.linalg.norm(np.cross(a, b), axis=1), np.abs(np.sum(a * b, axis=1)))
 
 
 # ------------------------------------------------------------------------------------- CPU tests
