@@ -22,8 +22,8 @@ from .registration import (fpfh_knn, icp_align, icp_correspondences,  # noqa: F4
 from .features import cloud_fpfh, fpfh_estimation  # noqa: F401
 from .gauss_sphere import (cloud_gauss_sphere_segment, gauss_sphere_params,  # noqa: F401
                            gauss_sphere_segment, gauss_sphere_space, gauss_sphere_vote)
-from .postprocess import (PostProcessParams, cluster_filter, plane_border,  # noqa: F401
-                          post_process_planes, refit_planes)
+from .postprocess import (PostProcessParams, cluster_filter, debug_pip_masks,  # noqa: F401
+                          plane_border, post_process_planes, refit_planes)
 from ._lib import DLG_REFIT_FAST, DLG_REFIT_PCL, LIB_PATH  # noqa: F401
 from ._lib import (DLG_OPT_LEAN_ROUNDS, DLG_OPT_PCL_REFIT_DEVICE, DLG_OPT_PRUNE,  # noqa: F401
                    DLG_OPT_NORMALS_FUSED, DLG_OPT_PRUNE_NP, DLG_OPT_PRUNE_TILE_SCORER, DLG_TILE_BF16, DLG_TILE_EXACT, DLG_TILE_MFMA,

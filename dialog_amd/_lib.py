@@ -44,7 +44,7 @@ SYMBOLS = [
     "dlg_icp_params_default", "dlg_icp_align", "dlg_icp_correspondences", "dlg_cull_stats",
     "dlg_fpfh_estimate", "dlg_cloud_fpfh",
     "dlg_sac_ia_params_default", "dlg_fpfh_knn", "dlg_sac_ia_score", "dlg_sac_ia_align",
-    "dlg_debug_live_bytes",
+    "dlg_debug_live_bytes", "dlg_debug_pip_masks",
     "dlg_gs_params_default", "dlg_gs_space", "dlg_gs_vote", "dlg_gs_segment",
     "dlg_cloud_gs_segment", "dlg_knn_stats",
 ]
@@ -314,6 +314,9 @@ def load():
                                       C.POINTER(C.c_double), i32p]
     L.dlg_debug_live_bytes.restype = C.c_int64
     L.dlg_debug_live_bytes.argtypes = [C.c_int]
+    L.dlg_debug_pip_masks.argtypes = [vp, C.POINTER(Points), C.POINTER(Planes), C.c_float,
+                                      C.c_uint32, i64p, i32p, C.POINTER(C.c_uint32), C.c_int64,
+                                      i64p]
     L.dlg_float_sums.argtypes = [vp, fp, C.c_int64, fp, C.c_int, fp, fp, C.POINTER(C.c_int),
                                  C.POINTER(C.c_double), i64p]
     L.dlg_ctx_set_option.argtypes = [vp, C.c_int, C.c_int64]

@@ -14,6 +14,7 @@
 #include <exception>
 #include <limits>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "driver.hpp"
@@ -255,6 +256,106 @@ void mark_nearest(dlg_ctx* c, int n, const BBox& b, int m) {
   HIPCHK(hipGetLastError());
 }
 
+// the absorption step (isPointInPoly) of postProcessPlanes up to the vote, shared by post_process and dlg_debug_pip_masks:
+// the candidates of the planes act[] (unprocessed points within t_dist of the plane `coeffs`
+// gives), their spatial sort, the tasks and k_pip_test.  Cloud in nw.x/y/z (bounding box b),
+// pw.processed set.  Leaves pw.cand (the candidates, grouped by plane), pw.mask (their ten ray
+// parities) and pw.offs on the device; offs[a] .. offs[a + 1] is the range of plane act[a].
+struct PipRanges {
+  std::vector<uint32_t> offs;
+  int max_cnt = 0;
+};
+
+PipRanges pip_masks(dlg_ctx* c, int n, const BBox& b, const dlg_planes* P, const float* coeffs,
+                    const std::vector<int>& act, float t_dist, uint32_t rand_seed) {
+  NormalsWork& w = c->nw;
+  PostWork& pw = c->pw;
+  const int na = (int)act.size();
+  PipRanges R;
+  const int64_t bsf = P->borders_stride_bytes / 4;
+  std::vector<float4> h_planes(na), h_rays((size_t)na * kPipRays);
+  std::vector<int64_t> h_eoff(na + 1, 0);
+  for (int a = 0; a < na; ++a) {
+    const int k = act[a];
+    h_eoff[a + 1] = h_eoff[a] + (P->border_offsets[k + 1] - P->border_offsets[k]);
+  }
+  std::vector<PipEdge> h_edges(h_eoff[na]);
+  for (int a = 0; a < na; ++a) {
+    const int k = act[a];
+    const float* cf = coeffs + 4 * k;
+    h_planes[a] = make_float4(cf[0], cf[1], cf[2], cf[3]);
+    const float* bor = P->borders + P->border_offsets[k] * bsf;
+    const int64_t nb = P->border_offsets[k + 1] - P->border_offsets[k];
+    plane_rays(bor, nb, bsf, cf, rand_seed, h_rays.data() + (size_t)a * kPipRays);
+    plane_edges(bor, nb, bsf, h_edges.data() + h_eoff[a]);
+  }
+  pw.planes.ensure(na);
+  pw.rays.ensure((size_t)na * kPipRays);
+  pw.edges.ensure(h_edges.size());
+  pw.edge_off.ensure(na + 1);
+  pw.offs.ensure(na + 1);
+  pw.abs_cnt.ensure(na);
+  const size_t nbk = (size_t)na * pip_blocks(n);
+  pw.bcnt.ensure(nbk);
+  pw.boff.ensure(nbk);
+  w.sort_tmp.ensure(pip_scan_tmp_bytes(nbk));
+  HIPCHK(hipMemcpyAsync(pw.planes.p, h_planes.data(), na * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(pw.rays.p, h_rays.data(), h_rays.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(pw.edges.p, h_edges.data(), h_edges.size() * sizeof(PipEdge), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(pw.edge_off.p, h_eoff.data(), (na + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(launch_pip_candidates(w.x.p, w.y.p, w.z.p, n, pw.processed.p, pw.planes.p, na,
+                               t_dist, pw.bcnt.p, pw.boff.p, w.sort_tmp.p,
+                               w.sort_tmp.cap, nullptr, pw.offs.p, c->stream));
+  R.offs.assign(na + 1, 0);
+  std::vector<uint32_t>& offs = R.offs;
+  HIPCHK(hipMemcpyAsync(offs.data(), pw.offs.p, (na + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+  sync(c);
+  const uint32_t total = offs[na];
+  for (int a = 0; a < na; ++a) R.max_cnt = std::max(R.max_cnt, (int)(offs[a + 1] - offs[a]));
+  if (total > 0) {
+    pw.cand.ensure(total);
+    pw.cand2.ensure(total);
+    pw.mask.ensure(total);
+    HIPCHK(hipMemsetAsync(pw.mask.p, 0, (size_t)total * 4, c->stream));
+    HIPCHK(launch_pip_candidates(w.x.p, w.y.p, w.z.p, n, pw.processed.p, pw.planes.p, na,
+                                 t_dist, pw.bcnt.p, pw.boff.p, nullptr, 0,
+                                 pw.cand2.p, pw.offs.p, c->stream));
+    {  // spatial order within each plane (Morton code over the cloud's bounding box)
+      float ext = 0.0f;
+      for (int k = 0; k < 3; ++k) ext = std::max(ext, b.hi[k] - b.lo[k]);
+      const float4 ls = make_float4(b.lo[0], b.lo[1], b.lo[2], ext > 0.0f ? 16383.0f / ext : 0.0f);
+      w.keys64.ensure(total);
+      w.keys_alt.ensure(total);
+      w.sort_tmp.ensure(pip_sort_tmp_bytes((int)total));
+      HIPCHK(launch_pip_sort(pw.cand2.p, (int)total, pw.offs.p, na, R.max_cnt, w.x.p, w.y.p, w.z.p,
+                             ls, reinterpret_cast<uint64_t*>(w.keys64.p),
+                             reinterpret_cast<uint64_t*>(w.keys_alt.p), pw.cand.p, w.sort_tmp.p,
+                             w.sort_tmp.cap, c->stream));
+    }
+    // tasks: 256 candidates x a run of edges; edges split so the launch fills the chip
+    int64_t cblocks = 0;
+    for (int a = 0; a < na; ++a) cblocks += (offs[a + 1] - offs[a] + 255) / 256;
+    const int64_t want = 8LL * 256;
+    const int64_t split = std::max<int64_t>(1, (want + cblocks - 1) / std::max<int64_t>(cblocks, 1));
+    std::vector<PipTask> tasks;
+    for (int a = 0; a < na; ++a) {
+      const int64_t nb = h_eoff[a + 1] - h_eoff[a];
+      const int64_t chunk = std::max<int64_t>(16, (nb + split - 1) / split);
+      const uint32_t cnt = offs[a + 1] - offs[a];
+      for (uint32_t cb = 0; cb < cnt; cb += 256)
+        for (int64_t e = 0; e < nb; e += chunk)
+          tasks.push_back(PipTask{a, (int32_t)(offs[a] + cb), (int32_t)std::min<uint32_t>(256, cnt - cb),
+                                  (int32_t)e, (int32_t)std::min(nb, e + chunk)});
+    }
+    pw.tasks.ensure(tasks.size());
+    HIPCHK(hipMemcpyAsync(pw.tasks.p, tasks.data(), tasks.size() * sizeof(PipTask), hipMemcpyHostToDevice, c->stream));
+    launch_pip_test(pw.tasks.p, (int)tasks.size(), pw.cand.p, w.x.p, w.y.p, w.z.p, pw.planes.p,
+                    pw.rays.p, pw.edges.p, pw.edge_off.p, pw.mask.p, c->stream);
+    HIPCHK(hipGetLastError());
+  }
+  return R;
+}
+
 // the refit runs on host threads while the device does the nearest-neighbour marking
 struct RefitJob {
   std::thread th;
@@ -315,7 +416,7 @@ void post_process(dlg_ctx* c, const dlg_points* cloud, const dlg_planes* P,
   }
   refit.wait();
 
-  // (2) absorption into planes [start, np) (:1530-1556)
+  // (2) absorption into planes [start, np) (:1530-1556): isPointInPoly
   std::vector<int> act;  // participating planes; a NaN plane accepts nothing (every test is NaN)
   for (int k = start; k < np; ++k)
     if (finite4(coeffs_out + 4 * k)) act.push_back(k);
@@ -323,86 +424,11 @@ void post_process(dlg_ctx* c, const dlg_points* cloud, const dlg_planes* P,
   std::vector<int64_t> abs_cnt_h(np, 0);
   int64_t abs_total = 0;
   if (na > 0) {
-    const int64_t bsf = P->borders_stride_bytes / 4;
-    std::vector<float4> h_planes(na), h_rays((size_t)na * kPipRays);
-    std::vector<int64_t> h_eoff(na + 1, 0);
-    for (int a = 0; a < na; ++a) {
-      const int k = act[a];
-      h_eoff[a + 1] = h_eoff[a] + (P->border_offsets[k + 1] - P->border_offsets[k]);
-    }
-    std::vector<PipEdge> h_edges(h_eoff[na]);
-    for (int a = 0; a < na; ++a) {
-      const int k = act[a];
-      const float* cf = coeffs_out + 4 * k;
-      h_planes[a] = make_float4(cf[0], cf[1], cf[2], cf[3]);
-      const float* bor = P->borders + P->border_offsets[k] * bsf;
-      const int64_t nb = P->border_offsets[k + 1] - P->border_offsets[k];
-      plane_rays(bor, nb, bsf, cf, prm->rand_seed, h_rays.data() + (size_t)a * kPipRays);
-      plane_edges(bor, nb, bsf, h_edges.data() + h_eoff[a]);
-    }
-    pw.planes.ensure(na);
-    pw.rays.ensure((size_t)na * kPipRays);
-    pw.edges.ensure(h_edges.size());
-    pw.edge_off.ensure(na + 1);
-    pw.offs.ensure(na + 1);
-    pw.abs_cnt.ensure(na);
-    const size_t nbk = (size_t)na * pip_blocks(n);
-    pw.bcnt.ensure(nbk);
-    pw.boff.ensure(nbk);
-    w.sort_tmp.ensure(pip_scan_tmp_bytes(nbk));
-    HIPCHK(hipMemcpyAsync(pw.planes.p, h_planes.data(), na * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(pw.rays.p, h_rays.data(), h_rays.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(pw.edges.p, h_edges.data(), h_edges.size() * sizeof(PipEdge), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(pw.edge_off.p, h_eoff.data(), (na + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_pip_candidates(w.x.p, w.y.p, w.z.p, n, pw.processed.p, pw.planes.p, na,
-                                 prm->t_dist_point_plane, pw.bcnt.p, pw.boff.p, w.sort_tmp.p,
-                                 w.sort_tmp.cap, nullptr, pw.offs.p, c->stream));
-    std::vector<uint32_t> offs(na + 1);
-    HIPCHK(hipMemcpyAsync(offs.data(), pw.offs.p, (na + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    const uint32_t total = offs[na];
-    int max_cnt = 0;
-    for (int a = 0; a < na; ++a) max_cnt = std::max(max_cnt, (int)(offs[a + 1] - offs[a]));
-    if (total > 0) {
-      pw.cand.ensure(total);
-      pw.cand2.ensure(total);
-      pw.mask.ensure(total);
-      HIPCHK(hipMemsetAsync(pw.mask.p, 0, (size_t)total * 4, c->stream));
-      HIPCHK(launch_pip_candidates(w.x.p, w.y.p, w.z.p, n, pw.processed.p, pw.planes.p, na,
-                                   prm->t_dist_point_plane, pw.bcnt.p, pw.boff.p, nullptr, 0,
-                                   pw.cand2.p, pw.offs.p, c->stream));
-      {  // spatial order within each plane (Morton code over the cloud's bounding box)
-        float ext = 0.0f;
-        for (int k = 0; k < 3; ++k) ext = std::max(ext, b.hi[k] - b.lo[k]);
-        const float4 ls = make_float4(b.lo[0], b.lo[1], b.lo[2], ext > 0.0f ? 16383.0f / ext : 0.0f);
-        w.keys64.ensure(total);
-        w.keys_alt.ensure(total);
-        w.sort_tmp.ensure(pip_sort_tmp_bytes((int)total));
-        HIPCHK(launch_pip_sort(pw.cand2.p, (int)total, pw.offs.p, na, max_cnt, w.x.p, w.y.p, w.z.p,
-                               ls, reinterpret_cast<uint64_t*>(w.keys64.p),
-                               reinterpret_cast<uint64_t*>(w.keys_alt.p), pw.cand.p, w.sort_tmp.p,
-                               w.sort_tmp.cap, c->stream));
-      }
-      // tasks: 256 candidates x a run of edges; edges split so the launch fills the chip
-      int64_t cblocks = 0;
-      for (int a = 0; a < na; ++a) cblocks += (offs[a + 1] - offs[a] + 255) / 256;
-      const int64_t want = 8LL * 256;
-      const int64_t split = std::max<int64_t>(1, (want + cblocks - 1) / std::max<int64_t>(cblocks, 1));
-      std::vector<PipTask> tasks;
-      for (int a = 0; a < na; ++a) {
-        const int64_t nb = h_eoff[a + 1] - h_eoff[a];
-        const int64_t chunk = std::max<int64_t>(16, (nb + split - 1) / split);
-        const uint32_t cnt = offs[a + 1] - offs[a];
-        for (uint32_t cb = 0; cb < cnt; cb += 256)
-          for (int64_t e = 0; e < nb; e += chunk)
-            tasks.push_back(PipTask{a, (int32_t)(offs[a] + cb), (int32_t)std::min<uint32_t>(256, cnt - cb),
-                                    (int32_t)e, (int32_t)std::min(nb, e + chunk)});
-      }
-      pw.tasks.ensure(tasks.size());
-      HIPCHK(hipMemcpyAsync(pw.tasks.p, tasks.data(), tasks.size() * sizeof(PipTask), hipMemcpyHostToDevice, c->stream));
-      launch_pip_test(pw.tasks.p, (int)tasks.size(), pw.cand.p, w.x.p, w.y.p, w.z.p, pw.planes.p,
-                      pw.rays.p, pw.edges.p, pw.edge_off.p, pw.mask.p, c->stream);
-      HIPCHK(hipGetLastError());
+    const PipRanges R = pip_masks(c, n, b, P, coeffs_out, act, prm->t_dist_point_plane,
+                                  prm->rand_seed);
+    const std::vector<uint32_t>& offs = R.offs;
+    const int max_cnt = R.max_cnt;
+    if (offs[na] > 0) {
       pw.absorbed.ensure((size_t)na * n);
       HIPCHK(hipMemsetAsync(pw.absorbed.p, 0, (size_t)na * n, c->stream));
       HIPCHK(hipMemsetAsync(pw.abs_cnt.p, 0, na * 4, c->stream));
@@ -458,6 +484,66 @@ void post_process(dlg_ctx* c, const dlg_points* cloud, const dlg_planes* P,
     HIPCHK(hipMemcpyAsync(rem_ids, pw.out.p, 4 * (size_t)kept, hipMemcpyDeviceToHost, c->stream));
   }
   sync(c);
+}
+
+// dlg_debug_pip_masks: the absorption step alone, up to the vote, on the caller's coefficients,
+// every cloud point unprocessed
+void debug_pip_masks(dlg_ctx* c, const dlg_points* cloud, const dlg_planes* P, float t_dist,
+                     uint32_t rand_seed, int64_t* offsets, int32_t* ids, uint32_t* masks,
+                     int64_t cap, int64_t* n_needed) {
+  check_points(cloud, "points", kMaxGridPoints);
+  if (!P || P->n_planes < 0) throw DlgError(DLG_ERR_INVALID, "planes: null or negative count");
+  if (!offsets || !n_needed) throw DlgError(DLG_ERR_INVALID, "offsets / n_needed are null");
+  const int np = P->n_planes;
+  for (int k = 0; k <= np; ++k) offsets[k] = 0;
+  *n_needed = 0;
+  if (np == 0) return;
+  if (!P->coeffs) throw DlgError(DLG_ERR_INVALID, "planes: coeffs are null");
+  check_offsets(P->border_offsets, np, "borders");
+  check_records(P->borders, P->border_offsets[np], P->borders_stride_bytes, "borders");
+  for (int k = 0; k < np; ++k)
+    if (P->border_offsets[k + 1] == P->border_offsets[k])
+      throw DlgError(DLG_ERR_INVALID, "plane " + std::to_string(k) + " has an empty border");
+  const int n = (int)cloud->n;
+  if ((int64_t)n * np > (int64_t)INT32_MAX)
+    throw DlgError(DLG_ERR_INVALID, "points x planes exceeds 2^31 (32-bit candidate offsets)");
+  if (n == 0) return;
+  PostWork& pw = c->pw;
+  const BBox b = upload_points(c, cloud);  // nw.x/y/z
+  pw.processed.ensure(n);
+  HIPCHK(hipMemsetAsync(pw.processed.p, 0, n, c->stream));
+  std::vector<int> act;
+  for (int k = 0; k < np; ++k)
+    if (finite4(P->coeffs + 4 * k)) act.push_back(k);
+  const int na = (int)act.size();
+  if (na == 0) return;
+  const PipRanges R = pip_masks(c, n, b, P, P->coeffs, act, t_dist, rand_seed);
+  const uint32_t total = R.offs[na];
+  std::vector<int64_t> cnt(np, 0);
+  for (int a = 0; a < na; ++a) cnt[act[a]] = R.offs[a + 1] - R.offs[a];
+  for (int k = 0; k < np; ++k) offsets[k + 1] = offsets[k] + cnt[k];
+  *n_needed = total;
+  if ((int64_t)total > cap)
+    throw DlgError(DLG_ERR_CAPACITY, "ids / masks too small: need " + std::to_string(total));
+  if (total == 0) return;
+  if (!ids || !masks) throw DlgError(DLG_ERR_INVALID, "ids / masks are null");
+  std::vector<int32_t> h_cand(total);
+  std::vector<uint32_t> h_mask(total);
+  HIPCHK(hipMemcpyAsync(h_cand.data(), pw.cand.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(h_mask.data(), pw.mask.p, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+  sync(c);
+  // the device holds each plane's candidates in spatial order: back to ascending point id
+  std::vector<std::pair<int32_t, uint32_t>> pr;
+  for (int a = 0; a < na; ++a) {
+    pr.clear();
+    for (uint32_t t = R.offs[a]; t < R.offs[a + 1]; ++t) pr.emplace_back(h_cand[t], h_mask[t]);
+    std::sort(pr.begin(), pr.end());
+    const int64_t o = offsets[act[a]];
+    for (size_t t = 0; t < pr.size(); ++t) {
+      ids[o + (int64_t)t] = pr[t].first;
+      masks[o + (int64_t)t] = pr[t].second;
+    }
+  }
 }
 
 // polyPointCloud (PlaneDetect.h:1376-1440) for one plane; see dlg_plane_border
@@ -612,6 +698,15 @@ dlg_status dlg_cluster_filter(dlg_ctx* ctx, const dlg_points* pts, float radius,
     if (!n_kept) throw DlgError(DLG_ERR_INVALID, "n_kept is null");
     *n_kept = 0;
     cluster_filter(ctx, pts, radius, t_cluster_num, kept_ids, cap, n_kept);
+  });
+}
+
+dlg_status dlg_debug_pip_masks(dlg_ctx* ctx, const dlg_points* cloud, const dlg_planes* planes,
+                               float t_dist, uint32_t rand_seed, int64_t* offsets, int32_t* ids,
+                               uint32_t* masks, int64_t cap, int64_t* n_needed) {
+  if (!ctx) return DLG_ERR_INVALID;
+  return guarded(ctx, [&] {
+    debug_pip_masks(ctx, cloud, planes, t_dist, rand_seed, offsets, ids, masks, cap, n_needed);
   });
 }
 

@@ -71,7 +71,9 @@ DLG_HD inline PipRay make_ray(V3 c, V3 dir) {
 }
 
 // isBothLineSegsIntersect(a, b, c, d) with the edge and ray terms precomputed;
-// pa_l1 = |a|_1, pc_l1 = |c|_1 (only used by the early out)
+// pa_l1 = |a|_1, pc_l1 = |c|_1 (only used by the early out).  The bounds of the two early outs
+// are derived by hand; tests/test_pp_math.py (host) and tests/test_postprocess_edges_gpu.py
+// (device) compare them with the literal test at those bounds.
 DLG_HD inline bool segs_intersect(V3 pa, V3 pb, V3 nab, float dab, float pa_l1, V3 pc,
                                   float pc_l1, const PipRay& r) {
   const V3 pa_pc = v3_sub(pc, pa);

@@ -130,6 +130,35 @@ def post_process_planes(cloud, planes, params: PostProcessParams | None = None,
     return coeffs[:P].copy(), absorbed, rem[:nrem.value].copy()
 
 
+def debug_pip_masks(cloud, planes, t_dist: float, rand_seed: int, ctx: Context | None = None):
+    """dlg_debug_pip_masks: isPointInPoly up to its vote, on the planes' `coeff` as given (4
+    floats, no refit; `points` may be absent) with every cloud point unprocessed -> per plane
+    (ascending int32 candidate ids, uint32 masks of the ten ray parities)."""
+    ctx = ctx or default_context()
+    a, pts = _points(cloud)
+    P = len(planes)
+    A = _PlaneArrays([dict(coeff=_get(pl, "coeff"), points=(), border=_get(pl, "border"))
+                      for pl in planes])
+    off = np.zeros(P + 1, np.int64)
+    need = C.c_int64(0)
+    cap = max(a.shape[0], 1)
+    L = _lib.load()
+    while True:
+        ids = np.empty(cap, np.int32)
+        masks = np.empty(cap, np.uint32)
+        st = L.dlg_debug_pip_masks(ctx.h, C.byref(pts), C.byref(A.s), float(t_dist),
+                                   int(rand_seed) & 0xffffffff,
+                                   off.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(ids),
+                                   masks.ctypes.data_as(C.POINTER(C.c_uint32)), cap,
+                                   C.byref(need))
+        if st == _lib.DLG_ERR_CAPACITY and need.value > cap:
+            cap = int(need.value)
+            continue
+        ctx.check(st)
+        break
+    return [(ids[off[k]:off[k + 1]].copy(), masks[off[k]:off[k + 1]].copy()) for k in range(P)]
+
+
 def cluster_filter(points, radius: float, t_cluster_num: int, ctx: Context | None = None):
     """clusterFilt (PlaneDetect.h:1582-1655) -> ascending indices of the points kept."""
     ctx = ctx or default_context()

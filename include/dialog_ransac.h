@@ -1083,6 +1083,19 @@ dlg_status dlg_float_sums(dlg_ctx* ctx, const float* xyz, int64_t n, const float
  * or pinned host buffers (pinned == 1), over all contexts and clouds.  The library's own count, so a
  * test can see a leak on a device it shares with other processes.  No context. */
 int64_t dlg_debug_live_bytes(int pinned);
+/* Debugging: the absorption step (isPointInPoly) of dlg_post_process_planes alone, up to its
+ * vote, so that a test can compare the device's crossing arithmetic ray by ray.  planes->coeffs are used as given (4 floats per
+ * plane: no refit, planes->points and point_offsets are not read) and every cloud point counts as
+ * unprocessed.  Per plane k, ids[offsets[k] .. offsets[k + 1]) are its candidates (the points
+ * within t_dist of their projection on the plane) in ascending order and masks[] their ray
+ * parities: bit i set when ray i of isPointInPoly (after srand(rand_seed)) crosses the border an
+ * odd number of times; the point is absorbed when >= 5 of the 10 bits are set.  A plane with a
+ * non-finite coefficient has an empty range; a plane without border vertices is refused.
+ * offsets: n_planes + 1.  *n_needed = offsets[n_planes], also reported with DLG_ERR_CAPACITY
+ * (cap < *n_needed: ids and masks are not written). */
+dlg_status dlg_debug_pip_masks(dlg_ctx* ctx, const dlg_points* cloud, const dlg_planes* planes,
+                               float t_dist, uint32_t rand_seed, int64_t* offsets, int32_t* ids,
+                               uint32_t* masks, int64_t cap, int64_t* n_needed);
 /* Execution-path options of a context.  Every setting gives identical results (planes, inliers,
  * counts): they only choose among equivalent device paths, for tests and measurement.  There are
  * no environment switches in the library. */

@@ -103,6 +103,9 @@ def lib():
         L.orc_msvc_rand.restype = C.c_uint32
         L.orc_is_point_in_poly.argtypes = [fp, fp, fp, C.c_int64, C.c_int64, C.c_float,
                                            C.c_uint32]
+        L.orc_segs_intersect.argtypes = [fp, fp, fp, fp]
+        L.orc_pip_parities.argtypes = [fp, fp, fp, C.c_int64, C.c_int64, C.c_float, C.c_uint32,
+                                       C.POINTER(C.c_uint32)]
         L.orc_compute_point_normal.argtypes = [fp, C.c_int64, C.c_int64, fp, fp]
         L.orc_refit_planes.argtypes = [C.c_int, fp, fp, C.c_int64, i64p, fp]
         L.orc_cluster_filter.argtypes = [fp, C.c_int64, C.c_int64, C.c_float, C.c_int, u8p]
@@ -390,6 +393,32 @@ def is_point_in_poly(p, coeff, border, t_dist, seed):
     b = np.ascontiguousarray(border, np.float32).reshape(-1, 3)
     return bool(lib().orc_is_point_in_poly(_f(q), _f(c), _f(b), b.shape[0], 3, float(t_dist),
                                            int(seed) & 0xffffffff))
+
+
+def segs_intersect(a, b, c, d):
+    """isBothLineSegsIntersect(a, b, c, d) of the reference, literally"""
+    v = [np.ascontiguousarray(x, np.float32) for x in (a, b, c, d)]
+    return bool(lib().orc_segs_intersect(*(_f(x) for x in v)))
+
+
+def pip_parities(points, coeff, border, t_dist, seed):
+    """isPointInPoly up to its vote, for every row of points -> (candidate flags (n,) bool,
+    masks (n,) uint32: bit i = parity of ray i's crossings; 0 for a non-candidate)."""
+    p, stride = _xyz(points)
+    c = np.ascontiguousarray(coeff, np.float32)
+    b = np.ascontiguousarray(border, np.float32).reshape(-1, 3)
+    n = p.shape[0]
+    cand = np.zeros(n, bool)
+    masks = np.zeros(n, np.uint32)
+    L = lib()
+    m = C.c_uint32(0)
+    base = p.ctypes.data
+    for i in range(n):
+        q = C.cast(base + 4 * stride * i, C.POINTER(C.c_float))
+        cand[i] = bool(L.orc_pip_parities(q, _f(c), _f(b), b.shape[0], 3, float(t_dist),
+                                          int(seed) & 0xffffffff, C.byref(m)))
+        masks[i] = m.value
+    return cand, masks
 
 
 def compute_point_normal(points):

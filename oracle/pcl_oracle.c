@@ -1209,7 +1209,9 @@ static orc_v3 orc_proj_to_plane(orc_v3 p, const float c[4]) {
   return o;
 }
 
-static int orc_segs_intersect(orc_v3 pa, orc_v3 pb, orc_v3 pc, orc_v3 pd) {
+/* isBothLineSegsIntersect(a, b, c, d), literally: the one statement of the crossing test */
+int orc_segs_intersect(const float a[3], const float b[3], const float c[3], const float e[3]) {
+  orc_v3 pa = v3_at(a), pb = v3_at(b), pc = v3_at(c), pd = v3_at(e);
   orc_v3 nab = v3_normalized(v3_sub(pb, pa));
   orc_v3 ncd = v3_normalized(v3_sub(pd, pc));
   orc_v3 pa_pc = v3_sub(pc, pa);
@@ -1239,8 +1241,11 @@ uint32_t orc_msvc_rand(uint32_t* state) {
   return (*state >> 16) & 0x7fffu;
 }
 
-int orc_is_point_in_poly(const float p[3], const float coeff[4], const float* border, int64_t nb,
-                         int64_t border_stride, float t_dist, uint32_t seed) {
+/* isPointInPoly up to its vote: returns whether the point is a candidate (dist <= t_dist and a
+ * border to test against); *mask bit i = parity of ray i's crossings with the border */
+int orc_pip_parities(const float p[3], const float coeff[4], const float* border, int64_t nb,
+                     int64_t border_stride, float t_dist, uint32_t seed, uint32_t* mask) {
+  *mask = 0;
   orc_v3 q = v3_at(p);
   orc_v3 pp = orc_proj_to_plane(q, coeff);
   float dist = orc_dist_p2p(q, pp);
@@ -1249,23 +1254,30 @@ int orc_is_point_in_poly(const float p[3], const float coeff[4], const float* bo
   uint32_t st = seed;
   orc_v3 pn = {coeff[0], coeff[1], coeff[2]};
   const float lambda = 10000.0f;
-  int odd = 0;
+  const float c[3] = {pp.x, pp.y, pp.z};
   for (int i = 0; i < 10; ++i) {
     int64_t index = (int64_t)((uint64_t)orc_msvc_rand(&st) % (uint64_t)nb);
     orc_v3 s = v3_at(border + index * border_stride);
     orc_v3 e = v3_at(border + (index == nb - 1 ? 0 : index + 1) * border_stride);
     orc_v3 dir = v3_normalized(v3_sub(e, s));
     orc_v3 dp = v3_normalized(v3_cross(dir, pn));
-    orc_v3 pl = {pp.x + lambda * dp.x, pp.y + lambda * dp.y, pp.z + lambda * dp.z};
+    const float pl[3] = {pp.x + lambda * dp.x, pp.y + lambda * dp.y, pp.z + lambda * dp.z};
     int count = 0;
     for (int64_t j = 0; j < nb; ++j) {
-      orc_v3 a = v3_at(border + j * border_stride);
-      orc_v3 b = v3_at(border + (j == nb - 1 ? 0 : j + 1) * border_stride);
-      if (orc_segs_intersect(a, b, pp, pl)) ++count;
+      const float* a = border + j * border_stride;
+      const float* b = border + (j == nb - 1 ? 0 : j + 1) * border_stride;
+      if (orc_segs_intersect(a, b, c, pl)) ++count;
     }
-    odd += count % 2;
+    *mask |= (uint32_t)(count % 2) << i;
   }
-  return odd >= 10 / 2;
+  return 1;
+}
+
+int orc_is_point_in_poly(const float p[3], const float coeff[4], const float* border, int64_t nb,
+                         int64_t border_stride, float t_dist, uint32_t seed) {
+  uint32_t mask;
+  if (!orc_pip_parities(p, coeff, border, nb, border_stride, t_dist, seed, &mask)) return 0;
+  return __builtin_popcount(mask) >= 10 / 2;
 }
 
 int orc_compute_point_normal(const float* xyz, int64_t n, int64_t stride, float plane[4],

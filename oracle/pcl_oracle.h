@@ -146,7 +146,14 @@ int64_t orc_preprocess(const float* xyz, int64_t n, int64_t stride, int translat
 
 /* ---- postProcessPlanes (PlaneDetect.h:1454-1579) and its parts ---- */
 uint32_t orc_msvc_rand(uint32_t* state);  /* MSVC CRT rand() on an explicit state */
-/* isPointInPoly (PlaneDetect.h:1891-1964) after srand(seed); border: nb vertices */
+/* isBothLineSegsIntersect(a, b, c, d) (PlaneDetect.h:1966-2015), literally */
+int orc_segs_intersect(const float a[3], const float b[3], const float c[3], const float d[3]);
+/* isPointInPoly up to its vote: returns whether p is a candidate (distance to its projection
+ * <= t_dist, nb > 0); *mask bit i = parity of ray i's crossings (0 when not a candidate) */
+int orc_pip_parities(const float p[3], const float coeff[4], const float* border, int64_t nb,
+                     int64_t border_stride, float t_dist, uint32_t seed, uint32_t* mask);
+/* isPointInPoly (PlaneDetect.h:1891-1964) after srand(seed); border: nb vertices:
+ * orc_pip_parities with at least 5 of the 10 bits set */
 int orc_is_point_in_poly(const float p[3], const float coeff[4], const float* border, int64_t nb,
                          int64_t border_stride, float t_dist, uint32_t seed);
 /* pcl::computePointNormal over all n points (features/normal_3d.h) [PCL-1.8 ext] */

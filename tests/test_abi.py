@@ -92,6 +92,19 @@ def test_knn_stats_is_exported():
     assert L.dlg_abi_version() == _lib.ABI_VERSION == 5
 
 
+def test_debug_pip_masks_is_exported():
+    """dlg_debug_pip_masks: an added debug entry under the same ABI version; the Python wrapper
+    exists and the call refuses a null context"""
+    L = _lib.load()
+    assert "dlg_debug_pip_masks" in _lib.SYMBOLS and hasattr(L, "dlg_debug_pip_masks")
+    assert "dlg_debug_pip_masks" in header_symbols()
+    assert callable(dialog_amd.debug_pip_masks)
+    need = C.c_int64(-1)
+    assert L.dlg_debug_pip_masks(None, None, None, 0.1, 0, None, None, None, 0,
+                                 C.byref(need)) == _lib.DLG_ERR_INVALID
+    assert L.dlg_abi_version() == _lib.ABI_VERSION == 5
+
+
 def test_no_device_fails_loudly(monkeypatch):
     """On a box without a gfx950 device the product refuses to run (no silent CPU path)."""
     try:

@@ -6,6 +6,11 @@ arithmetic literally; the reference has no tests or fixtures for this stage, so 
 pinned here by (a) the MSVC rand() known answers, (b) agreement of its 10-ray majority vote with
 an exact even-odd containment test away from the border, and (c) agreement of its BFS clusters
 with scipy's connected components.  The GPU path must match the oracle bit for bit.
+
+The scenes here are synth.postprocess_scene's stars.  The edges are elsewhere: the early outs of
+the crossing test on the host in tests/test_pp_math.py; the device's ray parities, the task
+split, the 1-NN ties and clusterFilt's thresholds in tests/test_postprocess_edges_gpu.py, on the
+scenes of tests/pp_cases.py, which tests/test_postprocess_edges.py checks on the CPU.
 """
 import ctypes as C
 
